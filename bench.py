@@ -13,6 +13,12 @@ per GPU (weak scaling), instance b has p_slip = 0.1 + 0.2*b/B_total, terminal
 expert trajectories per instance (irlmx.demos, seed 1234 + b).  Inputs are
 resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the K steps, writes the last timed step's
+outputs when ``--dump-outputs DIR`` is given, and prints the result line.
+Everything else described below (``first_steps``, the CPU baseline, ``config1``,
+the stream-copy rate, the rocprofv3 summary's figures, ``full_run``) is measured
+only with ``--full``.
+
 The headline times K steps after W warm-up steps (steady state: the first
 step's forward pass runs ~360k sweeps, later ones ~650).  ``first_steps``
 reports the run from theta0 = 1 including step 1: steps 1..25 timed one by one
@@ -77,14 +83,22 @@ def parse(argv=None):
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--size", type=int, default=None, help="override grid size")
     ap.add_argument("--batch", type=int, default=None, help="override instances per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (policy, svf, forward sweep "
+                         "counts, updated theta) as DIR/<name>.npy, float64, at most 64 MB in all (larger outputs: a "
+                         "fixed seeded sample); with the same arguments the inputs are identical from run to run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: first_steps, the CPU baseline, config 1, the "
+                         "stream-copy rate, the rocprofv3 summary's figures and (config c3, or --full-run) a whole irl "
+                         "run; the options below refine it.  Without --full only the timed steps run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config1", action="store_true", help="skip the config-1 (5x5) same-run timings")
-    ap.add_argument("--first-steps", type=int, default=FIRST_STEPS,
-                    help="steps from theta0 reported in first_steps (0: off)")
+    ap.add_argument("--first-steps", type=int, default=None,
+                    help=f"steps from theta0 reported in first_steps (with --full; default {FIRST_STEPS}, 0: off)")
     ap.add_argument("--cpu-sweeps", type=int, default=60, help="timed CPU sweeps per statement")
     fr = ap.add_mutually_exclusive_group()
     fr.add_argument("--full-run", dest="full_run", action="store_true", default=None,
-                    help="also run irl to convergence (maxent.py:240-252, eps 1e-4) on a fresh copy of the workload and "
+                    help="with --full: also run irl to convergence (maxent.py:240-252, eps 1e-4) on a fresh copy of the workload and "
                          "report it under full_run (not part of the headline); default on for config c3 (~11 s), "
                          "off for the others (c4 ~130 s, c5 ~65 s)")
     fr.add_argument("--no-full-run", dest="full_run", action="store_false")
@@ -92,12 +106,51 @@ def parse(argv=None):
     ap.add_argument("--full-run-max-steps", type=int, default=20000, help="cap on gradient steps of the full run")
     ap.add_argument("--no-compact", action="store_true", help="full run without compacting converged instances")
     ap.add_argument("--profile", default=None,
-                    help="profiles/<tag>_summary.json of a rocprofv3 run of this workload (default: newest); its "
+                    help="with --full: profiles/<tag>_summary.json of a rocprofv3 run of this workload (default: newest); its "
                          "kernel average and PMC HBM bytes are reported beside the live figures")
     args = ap.parse_args(argv)
+    if not args.full:
+        if args.full_run or args.first_steps:
+            ap.error("--full-run and --first-steps need --full")
+        args.full_run, args.first_steps = False, 0
+    if args.first_steps is None:
+        args.first_steps = FIRST_STEPS
     if args.full_run is None:
         args.full_run = args.config == "c3" and not args.size and not args.batch
     return args
+
+
+DUMP_BUDGET = 64 << 20   # bytes of --dump-outputs in all
+
+
+def sampled_outputs(arrays, budget=DUMP_BUDGET, seed=0):
+    """``{name: float64 array}`` of at most ``budget`` bytes in all: every array
+    whole when they fit, otherwise each array larger than 4096 elements cut to
+    the same fraction of its elements, flattened, at sorted positions drawn
+    without replacement from a generator seeded with ``seed`` -- the positions
+    depend on the shapes alone, so two runs of the same workload keep the same
+    elements."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    small = sum(v.nbytes for v in arrays.values() if v.size <= 4096)
+    large = sum(v.nbytes for v in arrays.values() if v.size > 4096)
+    if small + large <= budget:
+        return arrays
+    frac = (budget - small) / float(large)
+    rng = np.random.default_rng(seed)
+    out = {}
+    for k in sorted(arrays):
+        v = arrays[k]
+        if v.size > 4096:
+            idx = np.sort(rng.choice(v.size, size=int(v.size * frac), replace=False))
+            v = v.reshape(-1)[idx]
+        out[k] = v
+    return out
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, v in sampled_outputs(arrays).items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def _latest(pattern):
@@ -556,6 +609,7 @@ def main(argv=None):
     sweeps, bsweeps = [], []
 
     ctr_steps = []   # library event counters (persistent launches, per-sweep reruns) per step
+    last = {}        # --dump-outputs: what the last timed step computed (references only, no device work)
 
     def step(i, timed):
         e0, e1, e2 = ev[i]
@@ -568,6 +622,8 @@ def main(argv=None):
         irl.update(svf)
         sweeps.append(iters)
         bsweeps.append(irl.last_backward_sweeps if causal else torch.full_like(iters, 2 * S))
+        if i == n_all - 1 and args.dump_outputs:
+            last.update(policy=pi, svf=svf, forward_sweeps=iters)
         if c0 is not None:   # (untimed steps only: the counter read is a host call)
             c1 = ops.counters()
             ctr_steps.append((i, {k: c1[k] - c0[k] for k in c0 if c1[k] != c0[k]}))
@@ -576,6 +632,15 @@ def main(argv=None):
     elapsed, per_step = timed_steps(step, args.steps, args.warmup, barrier, torch.cuda.synchronize)
     elapsed_max = max_over_ranks(elapsed, dev)
     value, ms_per_step = headline(elapsed_max, per_gpu, world, args.steps)
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step (before any later step moves theta):
+        # the backward's policy, the forward's svf and sweep counts, and the updated theta
+        last["theta"] = irl.theta
+        if causal:
+            last["backward_sweeps"] = irl.last_backward_sweeps
+        path = args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}")
+        dump_outputs(path, {k: v.detach().cpu().numpy() for k, v in last.items()})
+        last.clear()
 
     # steps 1..first_steps from theta0 (after the timed region: never inside it)
     n_first = args.first_steps
@@ -619,7 +684,7 @@ def main(argv=None):
             # the state and weights stay on chip across sweeps, HBM carries the halo exchanges
             "algorithmic_bytes_per_launch": kd["bytes"] / kd["launches"],
         }
-        ppath = args.profile or _latest_profile(args.config)
+        ppath = (args.profile or _latest_profile(args.config)) if args.full else None
         default_cfg = not args.size and not args.batch
         if ppath and os.path.exists(ppath) and default_cfg:
             prof = json.load(open(ppath))
@@ -683,8 +748,9 @@ def main(argv=None):
                          "(the warm-up and timed steps are the first W + K); step 1's forward runs to convergence "
                          "from the unit reward (~360k sweeps at 128x128)")}
         out["counters"] = {k: ctr_end[k] - ctr_start[k] for k in ctr_end}
-        out["roofline"]["stream_copy_GBs"] = stream_copy_gbs(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"]["stream_copy_GBs"] = stream_copy_gbs(dev)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             t = cpu_sweep_times_all_cores(size, float(slips[0]), args.cpu_sweeps, causal, stay)
             out["cpu_baseline"] = cpu_baseline_from(t, float(k_b.mean()), float(k_f.mean()))
             out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]

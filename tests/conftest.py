@@ -19,6 +19,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 for p in (PKG_DIR, ORACLE_DIR):
     if p not in sys.path:
         sys.path.insert(0, p)
+sys.path.append(os.path.join(ROOT, "tools"))
+import golden_parts  # noqa: E402  (tools/golden_parts.py: fixtures above 1 MiB are stored in parts)
 
 
 def pytest_configure(config):
@@ -27,7 +29,7 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
+    return golden_parts.load(os.path.join(GOLDEN, name))
 
 
 def unpack_trajectories(flat, lens):

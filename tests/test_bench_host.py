@@ -81,11 +81,43 @@ def test_timed_steps_brackets_exactly_k_steps():
 
 
 def test_full_run_default():
-    """The default bench line (config 3) also runs irl to convergence (full_run);
-    the long configs and overridden workloads only on request."""
+    """The default --full bench line (config 3) also runs irl to convergence
+    (full_run); the long configs and overridden workloads only on request."""
     import bench
-    assert bench.parse([]).full_run is True
-    assert bench.parse(["--no-full-run"]).full_run is False
-    assert bench.parse(["--config", "c4"]).full_run is False
-    assert bench.parse(["--config", "c5", "--full-run"]).full_run is True
-    assert bench.parse(["--size", "64"]).full_run is False
+    assert bench.parse(["--full"]).full_run is True
+    assert bench.parse(["--full", "--no-full-run"]).full_run is False
+    assert bench.parse(["--full", "--config", "c4"]).full_run is False
+    assert bench.parse(["--full", "--config", "c5", "--full-run"]).full_run is True
+    assert bench.parse(["--full", "--size", "64"]).full_run is False
+
+
+def test_plain_run_measures_only_the_headline():
+    """Without --full nothing beside the timed steps runs: no whole irl run and
+    no steps beyond W + K; asking for either without --full is an error."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.full_run, a.first_steps, a.steps, a.warmup) == (False, False, 0, 7, 2)
+    assert bench.parse(["--full"]).first_steps == bench.FIRST_STEPS
+    assert bench.parse(["--full", "--first-steps", "0"]).first_steps == 0
+    for bad in (["--full-run"], ["--first-steps", "5"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path):
+    """--dump-outputs: outputs that fit are written whole as float64; larger ones
+    are cut to a seeded sample that depends on the shapes alone and fits the budget."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    arrs = {"policy": rng.uniform(size=(3, 500, 4)), "svf": rng.uniform(size=(3, 5000)),
+            "forward_sweeps": np.array([7, 9, 11], dtype=np.int64)}
+    whole = bench.sampled_outputs(arrs)
+    assert all(whole[k].dtype == np.float64 and np.array_equal(whole[k], arrs[k]) for k in arrs)
+    budget = 100_000
+    a, b = bench.sampled_outputs(arrs, budget), bench.sampled_outputs({k: v.copy() for k, v in arrs.items()}, budget)
+    assert sum(v.nbytes for v in a.values()) <= budget
+    assert all(np.array_equal(a[k], b[k]) for k in arrs)
+    assert np.array_equal(a["forward_sweeps"], [7.0, 9.0, 11.0])       # small arrays stay whole
+    assert 0 < a["svf"].size < arrs["svf"].size and np.isin(a["svf"], arrs["svf"]).all()
+    bench.dump_outputs(str(tmp_path / "out"), arrs)
+    assert sorted(os.listdir(tmp_path / "out")) == ["forward_sweeps.npy", "policy.npy", "svf.npy"]
+    assert np.array_equal(np.load(tmp_path / "out" / "policy.npy"), arrs["policy"])

@@ -17,7 +17,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from gen_npmath import big_args  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-Z = np.load(os.path.join(ROOT, "tests", "golden", "npmath.npz"))
+from conftest import load_golden  # noqa: E402
+
+Z = load_golden("npmath")
 
 
 @pytest.fixture(scope="module")

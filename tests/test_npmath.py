@@ -26,7 +26,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from gen_npmath import big_args  # noqa: E402
 
-Z = np.load(os.path.join(ROOT, "tests", "golden", "npmath.npz"))
+from conftest import load_golden  # noqa: E402
+
+Z = load_golden("npmath")
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -63,6 +63,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "irl-maxent_amd"))
 OUT = os.path.join(ROOT, "tests", "golden")
 
+import golden_parts          # noqa: E402  (tools/golden_parts.py: fixtures above 1 MiB are written in parts)
 import maxent_oracle as O  # noqa: E402
 from irlmx import demos    # noqa: E402  (the bench's own input generator: numpy only)
 
@@ -196,9 +197,8 @@ def main():
     files = {}
     for cfg, key, out in res:
         if key == "dense":
-            path = os.path.join(OUT, f"{cfg}.npz")
-            np.savez_compressed(path, **out)
-            print("wrote", path, os.path.getsize(path), "bytes")
+            for path in golden_parts.save(os.path.join(OUT, cfg), out):
+                print("wrote", path, os.path.getsize(path), "bytes")
             continue
         d = files.setdefault(cfg, {})
         for k, v in out.items():
@@ -206,14 +206,12 @@ def main():
     for cfg, d in files.items():
         if cfg.startswith("run_"):
             d["instances"] = np.array(sorted({int(k.split("__")[0]) for k in d}))
-            path = os.path.join(OUT, f"{cfg}.npz")
-            np.savez_compressed(path, **d)
-            print("wrote", path, os.path.getsize(path), "bytes")
+            for path in golden_parts.save(os.path.join(OUT, cfg), d):
+                print("wrote", path, os.path.getsize(path), "bytes")
             continue
         d["instances"] = np.array(sorted({int(k.split("__")[0]) for k in d if k.split("__")[0].isdigit()}))
-        path = os.path.join(OUT, f"full_{cfg}.npz")
-        np.savez_compressed(path, **d)
-        print("wrote", path, os.path.getsize(path), "bytes")
+        for path in golden_parts.save(os.path.join(OUT, f"full_{cfg}"), d):
+            print("wrote", path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
