@@ -1,13 +1,16 @@
-// Error reporting and version of the irlmx C ABI.  No C++ exception crosses
-// the ABI: failures return a negative code and leave a thread-local message.
+// Error reporting and version of the irlmx C ABI, and the host utilities the
+// launch paths share.  No C++ exception crosses the ABI: failures return a
+// negative code and leave a thread-local message.
 
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 
+#include "cluster.h"
 #include "common.h"
 
 namespace irlmx {
@@ -26,6 +29,32 @@ int hip_fail(hipError_t e, const char* what) {
   return IRLMX_EHIP;
 }
 
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return (e && *e) ? atoi(e) : dflt;
+}
+
+int device_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+  return cus;
+}
+
+int launch_capacity(const void* fn, int threads) {
+  const int f_cus = env_int("IRLMX_PLAN_CUS", 0), f_per = env_int("IRLMX_PLAN_GRID_PER_CU", 0);
+  if (f_cus > 0 && f_per > 0) return f_cus * f_per;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess) return 0;
+  return device_cus() * per_cu;
+}
+
+LaunchTestKnobs launch_test_knobs() {
+  const int tmo_ms = env_int("IRLMX_TEST_EXCHANGE_TIMEOUT_MS", 0);
+  return LaunchTestKnobs{env_int("IRLMX_TEST_NOT_RESIDENT", 0) ? 1 : 0, env_int("IRLMX_TEST_DROP_TILE", -1),
+                         tmo_ms > 0 ? (unsigned long long)tmo_ms * 100000ull : kGatherTicks};
+}
+
 static std::atomic<long long> g_counters[IRLMX_COUNTERS_LEN];
 
 void count_event(int which) {
@@ -38,6 +67,29 @@ void note_exchange_timeout(const char* shape) {
     fprintf(stderr,
             "irlmx: %s shape: an exchange timed out (a workgroup descheduled or a lost granule); the call was rerun "
             "on the per-sweep shape (counter rerun_timeout; IRLMX_STRICT_EXCHANGE=1 makes it an error)\n", shape);
+}
+
+int grid_launch_outcome(int* err_words, const char* label, hipStream_t st) {
+  char what[64];
+  int err = 0;
+  hipError_t e = hipMemcpyAsync(&err, err_words, sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    snprintf(what, sizeof(what), "%s sync", label);
+    return hip_fail(e, what);
+  }
+  if (!err) return 0;
+  const bool timeout = !(err & kErrNotResident);
+  if (timeout && env_int("IRLMX_STRICT_EXCHANGE", 0)) {
+    set_error("%s shape: exchange timed out (workgroups not co-resident?)", label);
+    return IRLMX_EHIP;
+  }
+  if (timeout) note_exchange_timeout(label);
+  count_event(timeout ? IRLMX_CTR_RERUN_TIMEOUT : IRLMX_CTR_RERUN_NOT_RESIDENT);
+  e = hipMemsetAsync(err_words, 0, 4 * sizeof(int), st);
+  if (e == hipSuccess) return kClusterNotResident;
+  snprintf(what, sizeof(what), "%s err reset", label);
+  return hip_fail(e, what);
 }
 
 __global__ void numpy_math_kernel(int op, const double* __restrict__ x, double* __restrict__ y, int64_t n) {

@@ -22,10 +22,7 @@ constexpr int kSptMaxQuadBwd = 16;
 constexpr int kSptMaxQuadBwdCW = 20;
 constexpr int kTMax = 16;          // max sweeps per block (= max ghost rows)
 constexpr int kSoloBwdT = 256;     // backward sweeps per block of a solo tile (no ghost rows)
-#ifndef IRLMX_RESCALE_EVERY
-#define IRLMX_RESCALE_EVERY 32
-#endif
-constexpr int kRescaleEvery = IRLMX_RESCALE_EVERY;  // backward: max blocks between rescales
+constexpr int kRescaleEvery = 32;  // backward: max blocks between rescales
 constexpr size_t kMaxLdsBytes = 160 * 1024;  // LDS per CU (one workgroup per CU)
 // Tile-summary granule slots per instance, indexed by block % kSumSlots.  A
 // backward tile reads the other tiles' summaries only on rescale blocks (at
@@ -64,7 +61,7 @@ struct ClusterArgs {
   long long max_iter;
   long long n_sweeps;      // backward: collapsed sweeps (2S - 1)
   int rescale;
-  unsigned long long* gran;   // [B][gran_inst_len] x 16-byte tagged granule pairs (halo rows, see kGranRowPad)
+  unsigned long long* gran;   // [B][gran_inst_len] x 16-byte tagged granule pairs (halo rows, see gran_par_len)
   unsigned long long* sgran;  // [B][kSumRows][H] x 16-byte tagged granule pairs (tile summaries, XCC ids, full flags)
   int xcd_group;           // number the tiles of an instance within one XCD group
   unsigned salt;           // per-launch granule tag salt
@@ -95,14 +92,12 @@ struct ClusterPlan {
 // counter, no fence, one fabric round trip per exchange.  Tag = per-launch
 // salt | (block + 1); the workspace is also zeroed before every call.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#ifndef IRLMX_POLL_SLEEP
-#define IRLMX_POLL_SLEEP 1   // s_sleep units (64 cycles) between polling passes
-#endif
+constexpr int kPollSleep = 1;  // s_sleep units (64 cycles) between polling passes
 constexpr int kGatherPerThread = 4;
 
-// Halo granule layout per instance: [2 parities][S states (+ kGranRowPad per
-// row)] x 16 B.  At width 128 the parities and the instances sit a few 128-B
-// lines further apart than their power-of-two sizes (24 and 40 granules); other
+// Halo granule layout per instance: [2 parities][S states] x 16 B.  At width
+// 128 the parities and the instances sit a few 128-B lines further apart than
+// their power-of-two sizes (24 and 40 granules); other
 // widths keep the power-of-two distances.  Measured (DESIGN.md section 4 "Halo
 // granule layout", profiles/r06_pad_ab.txt, r06_pmc_writeback.txt): the offsets
 // make the L2 write dirty granule lines back 4x as often (config 3's backward
@@ -110,21 +105,15 @@ constexpr int kGatherPerThread = 4;
 // backward 0.5-0.7 % faster on three boxes; at width 256 (config 4) the
 // unpadded layout is ~1 % faster.  IRLMX_GRAN_PAR_PAD / _INST_PAD (>= 0) force
 // one layout at every width.
-#ifndef IRLMX_GRAN_ROW_PAD
-#define IRLMX_GRAN_ROW_PAD 0
-#endif
 #ifndef IRLMX_GRAN_PAR_PAD
 #define IRLMX_GRAN_PAR_PAD -1
 #endif
 #ifndef IRLMX_GRAN_INST_PAD
 #define IRLMX_GRAN_INST_PAD -1
 #endif
-constexpr int kGranRowPad = IRLMX_GRAN_ROW_PAD;                   // extra granules per row (8: one 128-B line)
 __host__ __device__ inline size_t gran_par_pad(int W) { return IRLMX_GRAN_PAR_PAD >= 0 ? IRLMX_GRAN_PAR_PAD : (W == 128 ? 24 : 0); }
 __host__ __device__ inline size_t gran_inst_pad(int W) { return IRLMX_GRAN_INST_PAD >= 0 ? IRLMX_GRAN_INST_PAD : (W == 128 ? 40 : 0); }
-__host__ __device__ inline size_t gran_par_len(int W, int H) {
-  return (size_t)H * (W + kGranRowPad) + gran_par_pad(W);
-}
+__host__ __device__ inline size_t gran_par_len(int W, int H) { return (size_t)H * W + gran_par_pad(W); }
 __host__ __device__ inline size_t gran_inst_len(int W, int H) { return 2 * gran_par_len(W, H) + gran_inst_pad(W); }
 
 // A granule buffer: its descriptor (and, in IRLMX_DEVICE_CHECKS builds, its
@@ -190,7 +179,7 @@ __device__ inline bool gran_gather(const Gran& r, const Gran& rl, const unsigned
       }
     if (!pending) break;
     if (__builtin_amdgcn_s_memrealtime() - t0 > limit) return false;
-    __builtin_amdgcn_s_sleep(IRLMX_POLL_SLEEP);
+    __builtin_amdgcn_s_sleep(kPollSleep);
   }
   return true;
 }
@@ -266,6 +255,29 @@ constexpr int kClusterNonFinite = 1;
 // cluster_run's result when the launch's workgroups could not all run at once
 // (coresident()): the call must be rerun on a shape without hand-offs
 constexpr int kClusterNotResident = 2;
+
+// Outcome of a persistent launch of the grid or dense grid shape (`label` names
+// it in messages): reads err[0] on the stream (synchronises it).  0 when every
+// workgroup ran to the end.  When the rendezvous failed, or (after a passed
+// rendezvous) a workgroup was descheduled long enough for an exchange to time
+// out: counts the rerun, notes a timeout on stderr (note_exchange_timeout),
+// clears the four err words and returns kClusterNotResident -- the caller
+// reruns on the per-sweep shape.  IRLMX_STRICT_EXCHANGE=1 (tests) makes the
+// timeout an error instead.  (capi.hip; cluster_run keeps its own read-out.)
+int grid_launch_outcome(int* err, const char* label, hipStream_t st);
+
+// The launch paths' test-only environment reads.  IRLMX_TEST_NOT_RESIDENT=1:
+// the rendezvous waits for one workgroup more than launched, i.e. takes the
+// not-co-resident path deterministically.  IRLMX_TEST_DROP_TILE=<workgroup>
+// and IRLMX_TEST_EXCHANGE_TIMEOUT_MS=<ms>: that workgroup leaves after the
+// rendezvous, so its neighbours' exchange times out (after the shortened limit)
+// and the call takes the rerun path.
+struct LaunchTestKnobs {
+  int extra_resident;               // 1 or 0
+  int drop;                         // workgroup, else -1
+  unsigned long long gather_ticks;  // kGatherTicks unless shortened
+};
+LaunchTestKnobs launch_test_knobs();
 
 // compact: the backward's weights have the structure layout 4 needs
 // (bwd_compact_ok_kernel); the planner then considers it at width 256

@@ -52,9 +52,6 @@
 
 namespace irlmx {
 
-void set_error(const char* fmt, ...);
-int hip_fail(hipError_t e, const char* what);
-
 // LDS buffer layout: [W + 1 zeros][E states][W + 1 zeros].  With the pads, the
 // five stencil reads of state l are q[0], q[W-1], q[W], q[W+1], q[2W] for
 // q = buf + l + 1: one address register per state and constant offsets (the
@@ -129,31 +126,14 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   constexpr int HW = COLS ? WT / CPL : 1;                // COLS: lanes per band
   constexpr int NB = COLS ? NT / HW : 1;                 // COLS: bands
   constexpr int QW = CPL / 2;                            // COLS: double2 per lane per row
-#ifndef IRLMX_FWD_PROOF
-#define IRLMX_FWD_PROOF 1
-#endif
   // Forward, column layouts: per-sweep bookkeeping on band row kProofRow only
   // (the cheap proof of "not converged"; the block loop replays a block with
-  // full bookkeeping when some sweep is left unproven).  IRLMX_FWD_PROOF=0: full
-  // bookkeeping every sweep, as before round 6.
-  constexpr bool kProof = MODE == kModeFwd && COLS && IRLMX_FWD_PROOF;
+  // full bookkeeping when some sweep is left unproven).
+  constexpr bool kProof = MODE == kModeFwd && COLS;
   constexpr int kProofRow = RW / 2;
-#ifndef IRLMX_LDS_SIDES
-#define IRLMX_LDS_SIDES -1
-#endif
-  // COLS pairs: band edge rows' side neighbours from LDS (for quads, where 2 of
-  // 3 rows are edge rows, the exposed LDS latency costs more than the DPP moves).
-  // Forward only since round 5's backward schedule (store fence, unpinned
-  // barrier): DPP moves there are faster -- config 3's backward 22.09 / 22.13 ->
-  // 21.99 / 21.99 ms, config 2's 2.57 -> 2.40 ms -- while the forward keeps the
-  // LDS reads (one 128x128 instance 13.42 -> 13.82 ms per 20,000 sweeps with DPP;
-  // profiles/r05_ab_c3_sched.txt).  IRLMX_LDS_SIDES: -1 that rule, 0 never, 1 always.
-  constexpr bool kLdsSides = COLS && CPL == 2 && (IRLMX_LDS_SIDES < 0 ? MODE == kModeFwd : IRLMX_LDS_SIDES != 0);
-#ifndef IRLMX_COLS_RELOAD
-#define IRLMX_COLS_RELOAD 0
-#endif
-  // COLS: register state through the LDS tile at every block boundary (see the publish step)
-  constexpr bool kReload = COLS && IRLMX_COLS_RELOAD;
+  // Column pairs, forward: the band edge rows' side neighbours come from LDS;
+  // the backward and the quads use DPP moves (profiles/r05_ab_c3_sched.txt).
+  constexpr bool kLdsSides = COLS && CPL == 2 && MODE == kModeFwd;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int W = WT ? WT : a.W;
   const int H = a.H, S = a.S;
@@ -288,10 +268,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     bool mine = false;
 #pragma unroll
     for (int j = 0; j < SPT; ++j) mine |= !(c0[MODE == kModeFwd ? j : 0] == 0.0);
-#ifndef IRLMX_FWD_P0_SKIP
-#define IRLMX_FWD_P0_SKIP 1
-#endif
-    wave_p0 = !IRLMX_FWD_P0_SKIP || __builtin_amdgcn_readfirstlane(__builtin_amdgcn_ballot_w64(mine) != 0ull ? 1 : 0) != 0;
+    wave_p0 = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_ballot_w64(mine) != 0ull ? 1 : 0) != 0;
   }
   for (int i = tid; i < (COLS ? 1 : 2) * blen; i += NT) bufA[i] = 0.0;
   for (int i = tid; i < kBndLen; i += NT) bnd[i] = make_double2(0.0, 0.0);
@@ -465,17 +442,6 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   // band edge row e (0: top, 1: bottom) of band slot `band` (0 and NB + 1 are
   // the zero bands) in parity buffer `par`
   auto bnd_at = [&](int par, int band, int e) { return bnd + ((((size_t)par * (NB + 2) + band) * 2 + e) * HW + cp) * QW; };
-  // kSplitEdges (column pairs): the same storage per edge row as two arrays of
-  // HW doubles (column 0, column 1), so that the side reads -- the neighbour
-  // lanes' last / first column -- are 8-byte strided (no bank conflicts; the
-  // double2 form reads them at a 16-byte stride)
-#ifndef IRLMX_SPLIT_EDGES
-#define IRLMX_SPLIT_EDGES 0
-#endif
-  constexpr bool kSplitEdges = kLdsSides && IRLMX_SPLIT_EDGES;
-  auto edge_row = [&](int par, int band, int e) {
-    return reinterpret_cast<double*>(bnd + (((size_t)par * (NB + 2) + band) * 2 + e) * HW * QW);
-  };
   // p0tag (std::integral_constant<bool, P0>): with P0 false the forward's "p0 +"
   // is left out -- exact where every p0 of the wave's slots is +-0: the FMA
   // chain starts from fma(w, v, +0.0), which is never -0.0, so 0.0 + acc == acc
@@ -491,55 +457,21 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     if constexpr (COLS) {
       const unsigned ob = slot_bits(own_bits);
       double dmax = 0.0;
-#ifndef IRLMX_CW_PREFETCH
-#define IRLMX_CW_PREFETCH 1
-#endif
       // CW: the middle columns' self weights of every row, read at the top of
       // the sweep (constant LDS data: ahead of the edge-row stores and the
       // barrier) so that no row's FMA chain starts by waiting for its read
-      double2 wm_pf[CW && IRLMX_CW_PREFETCH ? RW : 1];
-      if constexpr (CW && IRLMX_CW_PREFETCH) {
+      double2 wm_pf[CW ? RW : 1];
+      if constexpr (CW) {
 #pragma unroll
         for (int r = 0; r < RW; ++r) wm_pf[r] = wmid[(bb * RW + r) * HW + cp];
       }
-#ifndef IRLMX_FWD_BRANCH_ACCOUNT
-#define IRLMX_FWD_BRANCH_ACCOUNT 1
-#endif
-#ifndef IRLMX_FWD_BRANCH_SPT_MAX
-#define IRLMX_FWD_BRANCH_SPT_MAX 12
-#endif
-      // With wave-uniform slot predicates (IRLMX_FWD_BRANCH_ACCOUNT): a scalar
-      // branch per slot around the owned-delta update instead of computing it
-      // for every slot and selecting -- the empty asm keeps the compiler from
-      // speculating the body back into selects.  One 128² instance's forward
-      // 0.736 -> 0.713 us per sweep, config 5 forward 127.0 -> 122.4 ms, same
-      // sweep counts.  Round 5: at 12 states per lane too (config 3's and the
-      // batched causal forward; two VGPRs spill, outside the sweep loop): B = 64
-      // at 128x128, 3,000 sweeps 3.19 -> 3.01 ms, three alternations on one box.
-#ifndef IRLMX_FWD_BALLOT_ACCOUNT
-#define IRLMX_FWD_BALLOT_ACCOUNT 0
-#endif
-#ifndef IRLMX_FWD_NO_ACCOUNT
-#define IRLMX_FWD_NO_ACCOUNT 0   // timing experiments only: every sweep counts as not converged
-#endif
-      // IRLMX_FWD_BALLOT_ACCOUNT=1 (round 6, measured slower): no branch and no
-      // select -- per slot one f64 subtract and one compare whose lane mask (a
-      // ballot, SGPRs) is ANDed with the slot's ownership and ORed into a
-      // wave-uniform mask, the sweep one straight-line block.  The same bit as
-      // the fmax form's (NaN > eps is false, as fmax drops NaN), but each
-      // compare-to-SGPR feeds a scalar OR: config 3's plan 11.4k -> 14.4k cycles
-      // of sweeps per 8-sweep block, one 128x128 instance 6.9k -> 9.1k.
-      constexpr bool kBallotAccount = MODE == kModeFwd && IRLMX_FWD_BALLOT_ACCOUNT;
-      unsigned long long anyv = 0ull;
+      // Forward with wave-uniform slot predicates: a scalar branch per slot
+      // around the owned-delta update instead of computing it for every slot and
+      // selecting -- the empty asm keeps the compiler from speculating the body
+      // back into selects (measured in DESIGN.md section 5, "Round 4 final").
       auto account = [&](int j, double nv, double self) {
         if (!kFull && j / CPL != kProofRow) return;   // (compile-time after unrolling)
-        if constexpr (MODE == kModeFwd && IRLMX_FWD_NO_ACCOUNT) {
-          (void)j; (void)nv; (void)self;
-        } else if constexpr (kBallotAccount) {
-          bool big = ((ob >> j) & 1u) != 0u;
-          big = big & (fabs(nv - self) > eps);
-          anyv |= __builtin_amdgcn_ballot_w64(big);
-        } else if constexpr (MODE == kModeFwd && kUniformSlots && SPT <= IRLMX_FWD_BRANCH_SPT_MAX && IRLMX_FWD_BRANCH_ACCOUNT) {
+        if constexpr (MODE == kModeFwd && kUniformSlots) {
           if ((ob >> j) & 1u) {
             asm volatile("");
             dmax = fmax(dmax, fabs(nv - self));
@@ -548,12 +480,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
           dmax = fmax(dmax, fabs(nv - self));
         }
       };
-      if constexpr (kSplitEdges) {  // band edge rows (old values) out: column 0 / column 1 arrays
-        double* t = edge_row(i & 1, bb + 1, 0);
-        double* u = edge_row(i & 1, bb + 1, 1);
-        t[cp] = src[0]; t[HW + cp] = src[1];
-        u[cp] = src[SPT - 2]; u[HW + cp] = src[SPT - 1];
-      } else {  // band edge rows (old values) out
+      {  // band edge rows (old values) out
         double2* t = bnd_at(i & 1, bb + 1, 0);
         double2* u = bnd_at(i & 1, bb + 1, 1);
 #pragma unroll
@@ -562,24 +489,13 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
           u[q] = make_double2(src[SPT - CPL + 2 * q], src[SPT - CPL + 2 * q + 1]);
         }
       }
-#ifndef IRLMX_PIN_STORES
-#define IRLMX_PIN_STORES -1
-#endif
-      // Column pairs: issue the band-edge stores before the first interior rows'
-      // FMAs, which then cover the stores' completion ahead of the barrier (the
-      // scheduler otherwise sinks the stores below most of those FMAs).  Faster
-      // for the backward at up to 8 states per lane -- config 2's solo backward
-      // 2.81 -> 2.56 ms, one 128x128 instance 17.16 -> 16.70 ms -- slower at 12
-      // (config 3: 22.51 -> 23.6 ms), neutral for the forward
-      // (profiles/r05_ab_pin_stores.txt).  IRLMX_PIN_STORES: -1 that rule, 0 never, 1 always.
-      // Config 3's backward (column pairs, 12 states per lane) is fastest with
-      // the store fence, both interior steps before the barrier and the barrier
-      // unpinned: 22.57 / 22.64 -> 22.24 / 22.23 ms (two alternations; at 8
-      // states per lane the same set is slower, config 2 2.57 -> 2.67 ms;
-      // profiles/r05_ab_c3_sched.txt)
+      // Column pairs, backward, at up to 8 or at 12 states per lane: issue the
+      // band-edge stores before the first interior rows' FMAs, which then cover
+      // the stores' completion ahead of the barrier (profiles/r05_ab_pin_stores.txt).
+      // At 12 (config 3's backward) the fence goes with both interior steps
+      // before the barrier and the barrier unpinned (profiles/r05_ab_c3_sched.txt).
       constexpr bool kBwdPairs12 = CPL == 2 && MODE == kModeBwd && SPT >= 12;
-      constexpr bool kPinStores =
-          IRLMX_PIN_STORES < 0 ? (CPL == 2 && MODE == kModeBwd && (SPT <= 8 || kBwdPairs12)) : IRLMX_PIN_STORES != 0;
+      constexpr bool kPinStores = CPL == 2 && MODE == kModeBwd && (SPT <= 8 || kBwdPairs12);
       if constexpr (kPinStores) __builtin_amdgcn_sched_barrier(0);
       if (MODE == kModeFwd && i == 0) {
         // forward: the block-start state into the LDS snapshot (for a stop inside
@@ -595,49 +511,30 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
       // The band's own top / bottom rows are in the edge array too, so their
       // horizontal neighbours (the last column of lane cp - 1, the first of lane
       // cp + 1) can be LDS reads instead of DPP moves: 8 fewer VALU instructions
-      // per sweep at 6 rows per band (config 3 backward 24.69 -> 24.40 ms).  A band row spans the full width, so lane 0 is
-      // x = 0 and lane HW - 1 is x = W - 1, whose out-of-row neighbour (weight 0)
-      // reads an adjacent, finite array entry.
+      // per sweep at 6 rows per band (config 3 backward 24.69 -> 24.40 ms; kLdsSides:
+      // the forward in column pairs).  A band row spans the full width, so lane 0
+      // is x = 0 and lane HW - 1 is x = W - 1, whose out-of-row neighbour (weight
+      // 0) reads an adjacent, finite array entry.
       double side[2][2];  // [top, bottom][left, right]
-      // (which: 1 = the row above, 2 = the row below, 3 = both; sync: the barrier first)
-#ifndef IRLMX_PIN_BARRIER
-#define IRLMX_PIN_BARRIER -1
-#endif
-      // Column pairs: keep the instruction scheduler from moving the interior
-      // rows' FMAs across the barrier (it hoisted the barrier to the top of the
-      // loop body; config 3 backward 24.4 -> 23.0 ms on one box).  Column
-      // quads are faster unpinned (267.6 vs 273.6 ms at config 4).
-      // (IRLMX_PIN_BARRIER: -1 pairs only, 0 never, 1 always.)
-      constexpr bool kPin = IRLMX_PIN_BARRIER < 0 ? (CPL == 2 && !kBwdPairs12) : IRLMX_PIN_BARRIER != 0;
-      auto edges_in = [&](int which = 3, bool sync = true) {
-        if (kPin && sync) __builtin_amdgcn_sched_barrier(0);
-        if (sync) __syncthreads();
-        if (kPin && sync) __builtin_amdgcn_sched_barrier(0);
-        if constexpr (kSplitEdges) {
-          const double* t = edge_row(i & 1, bb, 1);
-          const double* u = edge_row(i & 1, bb + 2, 0);
-          if (which & 1) { above[0] = t[cp]; above[1] = t[HW + cp]; }
-          if (which & 2) { below[0] = u[cp]; below[1] = u[HW + cp]; }
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {  // left: column 1 of lane cp - 1; right: column 0 of lane cp + 1
-            const double* o = edge_row(i & 1, bb + 1, e);
-            side[e][0] = o[HW + cp - 1];
-            side[e][1] = o[cp + 1];
-          }
-          return;
-        }
+      // Column pairs (but config 3's backward, kBwdPairs12): keep the instruction
+      // scheduler from moving the interior rows' FMAs across the barrier (it
+      // hoisted the barrier to the top of the loop body; config 3 backward 24.4 ->
+      // 23.0 ms on one box).  Column quads are faster unpinned (267.6 vs 273.6 ms
+      // at config 4).
+      constexpr bool kPin = CPL == 2 && !kBwdPairs12;
+      // the barrier, then the neighbouring bands' edge rows (and the side neighbours) in
+      auto edges_in = [&]() {
+        if (kPin) __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+        if (kPin) __builtin_amdgcn_sched_barrier(0);
         const double2* t = (CW && bb == 0) ? zrow + cp * QW : bnd_at(i & 1, bb, 1);
         const double2* u = (CW && bb == NB - 1) ? zrow + cp * QW : bnd_at(i & 1, bb + 2, 0);
 #pragma unroll
         for (int q = 0; q < QW; ++q) {
-          if (which & 1) {
-            const double2 x = t[q];
-            above[2 * q] = x.x; above[2 * q + 1] = x.y;
-          }
-          if (which & 2) {
-            const double2 y = u[q];
-            below[2 * q] = y.x; below[2 * q + 1] = y.y;
-          }
+          const double2 x = t[q];
+          above[2 * q] = x.x; above[2 * q + 1] = x.y;
+          const double2 y = u[q];
+          below[2 * q] = y.x; below[2 * q + 1] = y.y;
         }
         if constexpr (kLdsSides) {
 #pragma unroll
@@ -666,7 +563,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
           if constexpr (CW) {
             // the five-weight chain with w_1 = w_2 = w_x and the self term as
             // described at the top of the kernel
-            const double2 wm = IRLMX_CW_PREFETCH ? wm_pf[IRLMX_CW_PREFETCH ? jr : 0] : wmid[(bb * RW + jr) * HW + cp];
+            const double2 wm = wm_pf[jr];
             acc[0] = fma(edge_w[2 * jr], v[0], 0.0);
             acc[1] = fma(wm.x, v[1], 0.0);
             acc[2] = fma(wm.y, v[2], 0.0);
@@ -705,58 +602,35 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
       // arrival), the rest while the edge reads after the barrier are in flight.
       constexpr int step = CPL == 2 ? 2 : 1;
       constexpr int n_int = RW >= 3 ? (RW - 2 + step - 1) / step : 0;
-#ifndef IRLMX_KPRE
-#define IRLMX_KPRE -1
-#endif
-      // (IRLMX_KPRE >= 0: experiments, interior steps before the barrier.)  The
-      // compact-weight quads run all their interior rows before the barrier:
-      // config 4's backward 193.3 / 189.8 -> 186.5 / 183.8 ms (two alternations;
-      // config 3's column pairs are slower that way, 22.50 -> 22.54-22.64 ms,
-      // profiles/r05_ab_c4_sched.txt)
-      // (config 3's backward: both interior steps, see kBwdPairs12; the
-      // forward in column pairs at <= 8 states per lane -- config 5's one
-      // instance, 6 per lane -- none: 14.25 / 14.30 -> 13.59 / 13.56 ms per
-      // 20,000 sweeps, but config 3's forward at 12 is slower that way)
-      constexpr int kPre = IRLMX_KPRE >= 0 ? (IRLMX_KPRE < n_int ? IRLMX_KPRE : n_int)
-                           : (CW || kBwdPairs12) ? n_int
+      // kPre: all of them for the compact-weight quads and config 3's backward
+      // (kBwdPairs12), none for the forward in column pairs at up to 8 states
+      // per lane, else half (profiles/r05_ab_c4_sched.txt, r05_ab_c3_sched.txt).
+      constexpr int kPre = (CW || kBwdPairs12) ? n_int
                            : (CPL == 2 && MODE == kModeFwd && SPT <= 8) ? 0
                                                                        : (n_int + 1) / 2;
-      // IRLMX_QUAD_LAZY_ABOVE (quads): the row below is read at the barrier, the
-      // row above only before the band's top row, so the two edge rows are never
-      // live together (four doubles less register pressure; the hot loop has no
-      // scratch either way -- DESIGN.md section 4 "Registers").
-#ifndef IRLMX_QUAD_LAZY_ABOVE
-#define IRLMX_QUAD_LAZY_ABOVE 0
-#endif
-      constexpr bool kLazy = CPL == 4 && IRLMX_QUAD_LAZY_ABOVE;
-      constexpr int kFirst = kLazy ? 2 : 3;
 #pragma unroll
       for (int s = 0; s < n_int; ++s) {
-        if (s == kPre) edges_in(kFirst);
+        if (s == kPre) edges_in();
         const int jp = 1 + s * step;
         rows(jp, jp + step - 1 <= RW - 2 ? jp + step - 1 : jp);
       }
-      if constexpr (kPre >= n_int) edges_in(kFirst);
+      if constexpr (kPre >= n_int) edges_in();
       if constexpr (RW >= 2) {
         if constexpr (CPL == 2) rows(RW - 1, 0);
-        else { rows(RW - 1, RW - 1); if constexpr (kLazy) edges_in(1, false); rows(0, 0); }
+        else { rows(RW - 1, RW - 1); rows(0, 0); }
       } else {
-        if constexpr (kLazy) edges_in(1, false);
         rows(0, 0);
       }
-      if constexpr (MODE == kModeFwd && IRLMX_FWD_NO_ACCOUNT) flags |= 1u << i;
-      else if constexpr (kBallotAccount) flags |= (anyv != 0ull ? 1u : 0u) << i;
-      else if (MODE == kModeFwd) flags |= ((dmax > eps) ? 1u : 0u) << i;
+      if (MODE == kModeFwd) flags |= ((dmax > eps) ? 1u : 0u) << i;
     }
   };
 
   // Halo exchange in tagged granules (cluster.h): this instance's region of
-  // a.gran is [2 parities][H rows][W + kGranRowPad] x 16 B (cluster.h), of a.sgran [kSumRows][H tiles] x 16 B
+  // a.gran is [2 parities][H rows][W] x 16 B plus pads (cluster.h), of a.sgran [kSumRows][H tiles] x 16 B
   // (summaries by block % kSumSlots, then the XCC ids and the full forward flags).
   const size_t gpl = gran_par_len(W, H);
   const Gran rg = gran_rsrc(a.gran + (size_t)inst * 2 * gran_inst_len(W, H), 32u * (unsigned)gpl);
-  constexpr int kRG = WT ? WT + kGranRowPad : 0;  // granules per row (compile-time where the width is)
-  const unsigned rgw = WT ? kRG : (unsigned)(W + kGranRowPad);
+  const unsigned rgw = (unsigned)W;  // granules per row
   const unsigned gbase = (unsigned)e0 * rgw;
   // granule index of extended-tile state l in the parity-0 half
   auto gidx = [&](int l) { return gbase + (unsigned)(l / W) * rgw + (unsigned)(l % W); };
@@ -897,16 +771,12 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
         // the whole block, so each sweep stays one straight-line block
         block_sweeps(flags, Tm, std::integral_constant<bool, !kProof>{});
       }
-#ifndef IRLMX_POST_SWEEP_BARRIER
-#define IRLMX_POST_SWEEP_BARRIER 0
-#endif
       // CW: the band-edge array aliases the tile buffer the publication is
       // staged in, so the last sweep's edge reads must be done first.  The other
       // layouts' staging writes touch nothing a sweep reads (the tile buffer is
       // read only between blocks, behind the barriers there), so their waves go
-      // on to the publication as they finish (IRLMX_POST_SWEEP_BARRIER=1: the r04
-      // barrier here, A/B)
-      if constexpr (CW || IRLMX_POST_SWEEP_BARRIER) __syncthreads();
+      // on to the publication as they finish.
+      if constexpr (CW) __syncthreads();
     } else {
       run_sweeps(Tm, flags);
     }
@@ -942,11 +812,8 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     };
     if constexpr (COLS) {
       // a band's rows sit in one wave: stage them in the LDS tile first, so that
-      // the stores spread over all waves after the barrier below.  kReload: all
-      // owned rows, and the register state is read back from the tile after the
-      // exchange -- it is then not live across the exchange code, which fits the
-      // kernels in their register budget without scratch spills.
-      const unsigned pb = slot_bits(kReload ? own_bits : pub_bits);
+      // the stores spread over all waves after the barrier below.
+      const unsigned pb = slot_bits(pub_bits);
 #pragma unroll
       for (int jp = 0; jp < SPT / 2; ++jp)
         if ((pb >> (2 * jp)) & 1u)
@@ -978,20 +845,14 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     __syncthreads();  // the tile summary in red32[m & 1] (and COLS: the staged rows) complete
     if (!solo) {
       if (tid == 0) gran_store(rs, ((unsigned)(m % kSumSlots) * (unsigned)a.H + (unsigned)tile) * 16u, red32[m & 1], tag, plain);
-#ifndef IRLMX_PAIR_BATCHED_PUBLISH
-#define IRLMX_PAIR_BATCHED_PUBLISH 0
-#endif
-      if constexpr (COLS && CPL == 2 && !IRLMX_PAIR_BATCHED_PUBLISH) {
+      if constexpr (COLS && CPL == 2) {
         store_rows();
       } else if constexpr (COLS) {
         // column quads (width 256: 8 rows per thread): the staged rows, kPub per
         // thread at a time, all LDS reads in flight before the stores (the plain
         // loop waits out one LDS round trip per row): config 4 backward 302.6 ->
         // 293.6 ms; no gain for column pairs at width 128 (23.5 vs 23.7 ms)
-#ifndef IRLMX_KPUB
-#define IRLMX_KPUB 4
-#endif
-        constexpr int kPub = IRLMX_KPUB;
+        constexpr int kPub = 4;
         const int nA = pubA1 - own0, ntot = nA + (own1 - pubB0);
         for (int k0 = 0; k0 < ntot; k0 += kPub * NT) {
           int ls[kPub];
@@ -1149,8 +1010,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
         const int l = slot_state(2 * jp);
         const bool own = (ob >> (2 * jp)) & 1u, ext = (xb >> (2 * jp)) & 1u;
         double2 v = make_double2(cv[PAIR ? 2 * jp : 0], cv[PAIR ? 2 * jp + 1 : 0]);
-        if (kReload) v = ext ? *reinterpret_cast<const double2*>(cur + pad + l) : make_double2(0.0, 0.0);
-        else if (!own && ext) v = *reinterpret_cast<const double2*>(cur + pad + l);  // gathered ghost pair
+        if (!own && ext) v = *reinterpret_cast<const double2*>(cur + pad + l);  // gathered ghost pair
         if (MODE == kModeBwd && e_scale) {
           v.x = ldexp(v.x, e_scale);
           v.y = ldexp(v.y, e_scale);
@@ -1174,8 +1034,8 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     // after the post-staging barrier).  Measured (tools/diag/ab_passes.py, three
     // alternations on one box): one 128x128 instance's forward 14.53 -> 14.17 ms
     // per 20,000 sweeps without this barrier, but config 3's backward 22.50 ->
-    // 22.77 ms -- so only the forward drops it.  (IRLMX_POST_SWEEP_BARRIER=1: as r04.)
-    if constexpr (!COLS || CW || MODE == kModeBwd || IRLMX_POST_SWEEP_BARRIER) __syncthreads();
+    // 22.77 ms -- so only the forward drops it.
+    if constexpr (!COLS || CW || MODE == kModeBwd) __syncthreads();
     stamp(3);
     if (MODE == kModeBwd && done >= total) break;
   }
@@ -1300,18 +1160,6 @@ __global__ void bwd_compact_ok_kernel(const double* __restrict__ row_val, int W,
 }
 
 static std::atomic<unsigned> g_salt{1};  // per-launch tag salt (cluster.h granules)
-
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? atoi(e) : dflt;
-}
-
-static int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  return cus;
-}
 
 // CUs the planner plans for: the device's, or IRLMX_PLAN_CUS (tests: a planner
 // that believes in more CUs than exist produces a grid that cannot be
@@ -1542,21 +1390,15 @@ int cluster_run(int mode, const ClusterPlan& plan, ClusterArgs a, int B, hipStre
     (void)hipMemsetAsync(stamps, 0, sizeof(unsigned long long) * 8 * nwg, st);
   }
   a.stamps = stamps;
-  // IRLMX_TEST_NOT_RESIDENT=1 (tests only): wait for one workgroup more than
-  // the launch has, i.e. take the not-co-resident path deterministically
-  const int extra = env_int("IRLMX_TEST_NOT_RESIDENT", 0) ? 1 : 0;
-  // IRLMX_TEST_DROP_TILE=<workgroup> and IRLMX_TEST_EXCHANGE_TIMEOUT_MS=<ms> (tests
-  // only): one workgroup leaves after the rendezvous, so its neighbours' exchange
-  // times out (after the shortened limit) and the call takes the rerun path
-  a.test_drop = env_int("IRLMX_TEST_DROP_TILE", -1);
+  const LaunchTestKnobs tk = launch_test_knobs();  // tests only (cluster.h)
+  a.test_drop = tk.drop;
+  a.gather_ticks = tk.gather_ticks;
   a.eager_summary = env_int("IRLMX_EAGER_SUMMARY", 0) ? 1 : 0;
-  const int tmo_ms = env_int("IRLMX_TEST_EXCHANGE_TIMEOUT_MS", 0);
-  a.gather_ticks = tmo_ms > 0 ? (unsigned long long)tmo_ms * 100000ull : kGatherTicks;
   for (int b0 = 0; b0 < B; b0 += p.per_launch) {
     const int nb = std::min(p.per_launch, B - b0);
     a.b0 = b0;
     a.nb = nb;
-    a.n_resident = nb * p.C + extra;
+    a.n_resident = nb * p.C + tk.extra_resident;
     if (b0 > 0) {  // fresh rendezvous counters for this launch (err[1..2])
       e = hipMemsetAsync(a.err + 1, 0, 2 * sizeof(int), st);
       if (e != hipSuccess) return hip_fail(e, "cluster rendezvous reset");

@@ -12,7 +12,17 @@ namespace irlmx {
 constexpr int kWave = 64;
 constexpr int kStencilK = 5;  // self, +x, -x, +y, -y
 
-void count_event(int which);  // irlmx_counters (capi.hip): IRLMX_CTR_*
+// Host utilities shared by every translation unit (capi.hip).
+void set_error(const char* fmt, ...);           // irlmx_last_error's thread-local message
+int hip_fail(hipError_t e, const char* what);   // set_error from a HIP error; returns IRLMX_EHIP
+int env_int(const char* name, int dflt);        // integer environment knob; unset or empty: dflt
+int device_cus();                               // CUs of the current device, 0 without one
+// Workgroups of `threads` threads of kernel `fn` (no dynamic LDS) that can run
+// at once.  IRLMX_PLAN_CUS x IRLMX_PLAN_GRID_PER_CU: planning without a device
+// (the host-side sanitizer build, tools/sanitize); a launch always re-checks
+// co-residency on the device (coresident()), so a wrong figure cannot hang.
+int launch_capacity(const void* fn, int threads);
+void count_event(int which);  // irlmx_counters: IRLMX_CTR_*
 // An exchange timed out and the call is rerun per sweep (capi.hip): the first
 // time in a process a line on stderr, so a lost or mistagged granule does not
 // pass silently as a slow success (the counter records every one).

@@ -59,14 +59,8 @@ constexpr int kDenseThreads = 256;
 // one instance; with several instances the vector re-reads compete with the
 // row streams in L1/L2 (S = 2048, B = 16: backward 36 us with LDS, 47 without;
 // forward 108 vs 158), so there it is staged (dense_lds_vec).
-#ifndef IRLMX_DENSE_RPW
-#define IRLMX_DENSE_RPW 2
-#endif
-#ifndef IRLMX_DENSE_UNROLL
-#define IRLMX_DENSE_UNROLL 4
-#endif
-constexpr int kDenseRowsPerWave = IRLMX_DENSE_RPW;
-constexpr int kDenseUnroll = IRLMX_DENSE_UNROLL;  // wave_dot: loop iterations whose loads issue together
+constexpr int kDenseRowsPerWave = 2;
+constexpr int kDenseUnroll = 4;  // wave_dot: loop iterations whose loads issue together
 constexpr int kDenseRowsPerBlock = (kDenseThreads / kWave) * kDenseRowsPerWave;
 constexpr int kDenseLdsMaxStates = 8192;  // the swept vector fits in LDS up to here (64 KiB)
 

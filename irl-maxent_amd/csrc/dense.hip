@@ -445,10 +445,7 @@ dense_bellman_finish_kernel(DenseView d, DenseBellman a, DenseBufs w) {
 // rows start 16-byte aligned only when S is even (V2: two 16-byte loads per
 // operand row and chunk), else the kernel loads doubles one by one.
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-#ifndef IRLMX_GEMM_PF
-#define IRLMX_GEMM_PF 1
-#endif
-constexpr int kGemmPrefetch = IRLMX_GEMM_PF;  // K chunks whose loads are in flight during a chunk's MFMAs
+constexpr int kGemmPrefetch = 1;  // K chunks whose loads are in flight during a chunk's MFMAs
 
 // ST 16-row tiles of M and NBT 16-instance column tiles per workgroup (sized to
 // S and B so that the grid fills the chip)

@@ -43,25 +43,16 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
 
 #include "cluster.h"
 #include "dense.h"
 
 namespace irlmx {
 
-void set_error(const char* fmt, ...);
-int hip_fail(hipError_t e, const char* what);
-
 namespace {
 
 constexpr int kDG = kDenseGridThreads;
 constexpr int kDGWaves = kDG / kWave;
-
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? atoi(e) : dflt;
-}
 
 template <int CTRL, int ROW_MASK>
 __device__ inline double dpp_f64(double v) {
@@ -577,22 +568,7 @@ void* dense_grid_fn(int mode, int rb, int cpt) {
   return mode == kModeFwd ? dense_grid_fn_mode<kModeFwd>(rb, cpt) : dense_grid_fn_mode<kModeBwd>(rb, cpt);
 }
 
-int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  return cus;
-}
-
-// workgroups of `fn` that can run at once; IRLMX_PLAN_CUS x IRLMX_PLAN_GRID_PER_CU
-// plan without a device (tools/sanitize); a launch re-checks on the device
-int capacity(void* fn) {
-  const int f_cus = env_int("IRLMX_PLAN_CUS", 0), f_per = env_int("IRLMX_PLAN_GRID_PER_CU", 0);
-  if (f_cus > 0 && f_per > 0) return f_cus * f_per;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, kDG, 0) != hipSuccess) return 0;
-  return device_cus() * per_cu;
-}
+int capacity(void* fn) { return launch_capacity(fn, kDG); }
 
 std::atomic<unsigned> g_dg_salt{1};
 
@@ -694,34 +670,16 @@ static int launch_grid(void* fn, const DenseGridPlan& p, DenseGridArgs a, int ro
   a.nb = a.B;
   a.xcd_group = p.xcd;
   a.salt = g_dg_salt.fetch_add(1, std::memory_order_relaxed);
-  // (IRLMX_TEST_NOT_RESIDENT=1, tests only: one workgroup more than launched -> the per-sweep rerun)
-  a.n_resident = p.bpi * a.B + (env_int("IRLMX_TEST_NOT_RESIDENT", 0) ? 1 : 0);
-  // (IRLMX_TEST_DROP_TILE / IRLMX_TEST_EXCHANGE_TIMEOUT_MS, tests only: one workgroup
-  // leaves after the rendezvous, its neighbours time out -> the per-sweep rerun)
-  a.test_drop = env_int("IRLMX_TEST_DROP_TILE", -1);
-  const int tmo_ms = env_int("IRLMX_TEST_EXCHANGE_TIMEOUT_MS", 0);
-  a.gather_ticks = tmo_ms > 0 ? (unsigned long long)tmo_ms * 100000ull : kGatherTicks;
+  const LaunchTestKnobs tk = launch_test_knobs();  // tests only (cluster.h)
+  a.n_resident = p.bpi * a.B + tk.extra_resident;
+  a.test_drop = tk.drop;
+  a.gather_ticks = tk.gather_ticks;
   const int grid = p.xcd ? 8 * ((a.B + 7) / 8) * p.bpi : p.bpi * a.B;
   void* args[] = {&a};
   hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kDG), args, 0, st);
   if (e != hipSuccess) return hip_fail(e, "dense grid launch");
   count_event(IRLMX_CTR_GRID_LAUNCHES);
-  int err = 0;
-  e = hipMemcpyAsync(&err, a.err, sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail(e, "dense grid sync");
-  const bool timeout = err && !(err & kErrNotResident);
-  if (timeout && env_int("IRLMX_STRICT_EXCHANGE", 0)) {
-    set_error("dense grid shape: exchange timed out (workgroups not co-resident?)");
-    return IRLMX_EHIP;
-  }
-  if (timeout) note_exchange_timeout("dense grid");
-  if (err) {  // not all workgroups ran at once, or an exchange timed out: the per-sweep shape
-    count_event(timeout ? IRLMX_CTR_RERUN_TIMEOUT : IRLMX_CTR_RERUN_NOT_RESIDENT);
-    e = hipMemsetAsync(a.err, 0, 4 * sizeof(int), st);
-    return e == hipSuccess ? kClusterNotResident : hip_fail(e, "dense grid err reset");
-  }
-  return 0;
+  return grid_launch_outcome(a.err, "dense grid", st);
 }
 
 int dense_bellman_grid_run(bool soft, const DenseGridPlan& p, DenseGridArgs a, hipStream_t st) {

@@ -41,15 +41,7 @@
 
 namespace irlmx {
 
-void set_error(const char* fmt, ...);
-int hip_fail(hipError_t e, const char* what);
-
 constexpr int kFusedMaxStates = 4096;
-
-static int getenv_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? atoi(e) : dflt;
-}
 
 // Largest S run by the fused shape; IRLMX_FUSED_MAX_STATES lowers it (tests use
 // 0 to drive every size through the sweep shape).
@@ -2178,23 +2170,10 @@ static void* grid_fn(const Model& m, int op, int spt) {
   return nullptr;
 }
 
-static int grid_capacity(void* fn) {
-  // IRLMX_PLAN_CUS x IRLMX_PLAN_GRID_PER_CU: planning without a device (the
-  // host-side sanitizer build, tools/sanitize); a launch always re-checks
-  // co-residency on the device (coresident()), so a wrong figure cannot hang
-  const int f_cus = getenv_int("IRLMX_PLAN_CUS", 0), f_per = getenv_int("IRLMX_PLAN_GRID_PER_CU", 0);
-  if (f_cus > 0 && f_per > 0) return f_cus * f_per;
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, kGridThreads, 0) != hipSuccess) return 0;
-  return cus * per_cu;
-}
-
 // the smallest states-per-thread whose grid is co-resident (all workgroups must
 // run at once: they wait on each other's granules); IRLMX_GRID=0 disables
 static bool grid_plan(const Model& m, int op, GridPlan* out) {
-  if (m.dense || getenv_int("IRLMX_GRID", 1) == 0) return false;
+  if (m.dense || env_int("IRLMX_GRID", 1) == 0) return false;
   if (m.S <= fused_max_states()) return false;  // one workgroup holds it: the fused shape
   if (op == IRLMX_OP_SOFT_BACKWARD || op == IRLMX_OP_VALUE_ITERATION) {
     if (m.A > kGridMaxActions || !grid_kmax(m)) return false;
@@ -2209,11 +2188,11 @@ static bool grid_plan(const Model& m, int op, GridPlan* out) {
     if (!fn) continue;
     const int bpi = (m.S + spt * kGridThreads - 1) / (spt * kGridThreads);
     if (bpi > kGridThreads) continue;  // the block maxima are gathered one per thread
-    const int cap = grid_capacity(fn);
+    const int cap = launch_capacity(fn, kGridThreads);
     // XCD groups: ceil(B / 8) instances per group, each group within one XCD's
     // share -- only from 8 instances on: fewer would leave XCDs idle (one 128x128
     // instance: soft VI 3.5 ms grouped on one XCD vs 3.1 ms spread, 812 sweeps)
-    const bool xcd = getenv_int("IRLMX_XCD_GROUP", 1) != 0 && cap >= 8 && m.B >= 8 &&
+    const bool xcd = env_int("IRLMX_XCD_GROUP", 1) != 0 && cap >= 8 && m.B >= 8 &&
                      (long long)((m.B + 7) / 8) * bpi <= cap / 8;
     if (xcd || (long long)bpi * m.B <= cap) {
       *out = GridPlan{spt, bpi, xcd ? 1 : 0};
@@ -2232,31 +2211,13 @@ static int grid_launch(const Model& m, int op, const GridPlan& gp, void** args, 
   hipError_t e = hipLaunchKernel(grid_fn(m, op, gp.spt), dim3(grid), dim3(kGridThreads), args, 0, st);
   if (e != hipSuccess) return hip_fail(e, "grid launch");
   count_event(IRLMX_CTR_GRID_LAUNCHES);
-  int err = 0;
-  e = hipMemcpyAsync(&err, ws.err, sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail(e, "grid sync");
-  // not all workgroups could run at once, or (after a passed rendezvous) one was
-  // descheduled long enough for an exchange to time out: clear the words and
-  // rerun on the per-sweep shape (cluster_run treats both cases the same way)
-  const bool timeout = err && !(err & kErrNotResident);
-  if (timeout && getenv_int("IRLMX_STRICT_EXCHANGE", 0)) {
-    set_error("grid shape: exchange timed out (workgroups not co-resident?)");
-    return IRLMX_EHIP;
-  }
-  if (timeout) note_exchange_timeout("grid");
-  if (err) {
-    count_event(timeout ? IRLMX_CTR_RERUN_TIMEOUT : IRLMX_CTR_RERUN_NOT_RESIDENT);
-    e = hipMemsetAsync(ws.err, 0, 4 * sizeof(int), st);
-    return e == hipSuccess ? kClusterNotResident : hip_fail(e, "grid err reset");
-  }
-  return 0;
+  return grid_launch_outcome(ws.err, "grid", st);
 }
 
 static GridArgs grid_args(const Model& m, const GridPlan& gp, const Ws& ws) {
-  // (IRLMX_TEST_NOT_RESIDENT=1, tests only: one workgroup more than launched -> the per-sweep rerun)
+  // (launch_test_knobs, tests only: one workgroup more than launched -> the per-sweep rerun)
   return GridArgs{ws.gran, ws.sgran, ws.err, gp.bpi, m.B, gp.xcd, g_grid_salt.fetch_add(1, std::memory_order_relaxed),
-                  gp.bpi * m.B + (getenv_int("IRLMX_TEST_NOT_RESIDENT", 0) ? 1 : 0)};
+                  gp.bpi * m.B + launch_test_knobs().extra_resident};
 }
 
 __global__ void fill_kernel(double* p, size_t n, double v) {
@@ -2307,7 +2268,7 @@ static bool fused_shape(const Model& m, int op, FusedShape* out) {
   // 4-5x faster than the general-sparsity fused kernel, and a single instance
   // then spreads over several CUs (cluster.hip).
   if ((op == IRLMX_OP_FORWARD || op == IRLMX_OP_BACKWARD) && m.stencil && (m.W == 64 || m.W == 128) &&
-      getenv_int("IRLMX_CLUSTER", 1) != 0)
+      env_int("IRLMX_CLUSTER", 1) != 0)
     return false;
   const int K = op == IRLMX_OP_FORWARD ? m.Kc : m.K;
   const int kmax = pick_kmax(K);
@@ -2462,7 +2423,7 @@ static DenseBufs dense_bufs(const Ws& ws) {
 // that cache (S >= 4096).  IRLMX_DENSE_GEMM_MIN=<B> forces the batch threshold.
 static bool dense_gemm(const Model& m) {
   if (!m.dense || !m.shared) return false;
-  const int forced = getenv_int("IRLMX_DENSE_GEMM_MIN", 0);
+  const int forced = env_int("IRLMX_DENSE_GEMM_MIN", 0);
   if (forced > 0) return m.B >= forced;
   return m.B >= 16 || (m.S >= 4096 && m.B >= 4);
 }
@@ -2552,7 +2513,7 @@ static bool bwd_compact_check(const Model& m, int* flag, hipStream_t st) {
   return h == 0;
 }
 static bool bwd_compact(const Model& m, int* flag, hipStream_t st) {
-  if (!m.stencil || m.W != 256 || getenv_int("IRLMX_COMPACT", 1) == 0) return false;
+  if (!m.stencil || m.W != 256 || env_int("IRLMX_COMPACT", 1) == 0) return false;
   if (m.props & IRLMX_PROPS_KNOWN) return (m.props & IRLMX_PROP_COMPACT) != 0;
   return bwd_compact_check(m, flag, st);
 }
@@ -2936,7 +2897,7 @@ static int bellman_common(const irlmx_mdp* mdp, const double* reward, const doub
   const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
   // the Bellman sweep is a latency chain per state (A dots, A softmax folds):
   // smaller workgroups spread one instance over more CUs (IRLMX_BELLMAN_THREADS)
-  const int bt = std::max(64, std::min(kSweepThreads, getenv_int("IRLMX_BELLMAN_THREADS", kSweepThreads)));
+  const int bt = std::max(64, std::min(kSweepThreads, env_int("IRLMX_BELLMAN_THREADS", kSweepThreads)));
   const dim3 gb((m.S + bt - 1) / bt, m.B);
   const size_t n = (size_t)m.B * m.S;
   hipLaunchKernelGGL(fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ws.buf0, n, soft ? -1e200 : 0.0);

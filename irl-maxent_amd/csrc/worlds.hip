@@ -19,8 +19,6 @@ namespace irlmx {
 // largest grid side / state count the 32-bit state indices of the kernels cover
 constexpr int kMaxSide = 46340;                    // size * size < 2^31
 constexpr long long kMaxStates = 46340LL * 46340LL;
-void set_error(const char* fmt, ...);
-int hip_fail(hipError_t e, const char* what);
 
 // action offsets, gridworld.py:47
 __device__ __constant__ int kActDx[4] = {1, -1, 0, 0};

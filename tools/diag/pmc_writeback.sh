@@ -4,7 +4,9 @@
 # (build/<name>/libirlmx.so from tools/diag/build_variant.sh; default list:
 # gran_pad0 = IRLMX_GRAN_PAR_PAD = IRLMX_GRAN_INST_PAD = 0).  Each counter set
 # is its own rocprofv3 pass (at most 4 TCC counters per pass).
-#   VARIANTS="default resc16" tools/diag/pmc_writeback.sh [SIZE B [OUTDIR]]
+#   VARIANTS="default gran_pad0" tools/diag/pmc_writeback.sh [SIZE B [OUTDIR]]
+# (a variant with another rescale period needs an edit of kRescaleEvery in
+# csrc/cluster.h before build_variant.sh: no flag sets it)
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/${3:-pmc_wb}
 VARIANTS=${VARIANTS:-default gran_pad0}
