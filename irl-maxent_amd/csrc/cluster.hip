@@ -80,6 +80,112 @@ __device__ inline double dpp_shift_f64(double x) {
   return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
 
+// Trapezoid schedule (backward, column pairs, width 128, 12 states per lane,
+// R = 32, G = T = 8, C >= 2 tiles of exactly R rows: config 3's plan).  A ghost
+// row at distance d from the owned rows feeds an owned row's block-end value
+// only through sweeps 1 .. T - d of a T-sweep block, so the equal-height bands
+// sweep 72 of 384 (edge tiles: 92) row-sweeps per block that nobody reads.  Here the
+// bands have unequal heights, the 8 sweeps of a block are unrolled, and row j
+// of a band is computed at sweep I only if it is owned or d <= T - I.  A
+// skipped row keeps a stale value, which only rows that are themselves dead
+// could read: the owned rows' values are bit for bit those of the full sweep
+// (the static_asserts below check the row sets against the dependency cone).
+//
+// Band kinds: height, and the ghost distance of band row j = max(0, d0 + ds * j)
+// (0: owned).  0 / 3 (g): the pure ghost rows d = 8 .. 2 above / below the
+// owned rows; 1 / 2 (m): the ghost row d = 1 and five owned rows; 4, 5, 6:
+// six, five, four owned rows.  Kind 7 sweeps seven rows with nothing skipped
+// (blocks shorter than T sweeps -- the last block, a capped rescale period --
+// and a.trap_noskip run every band by its height alone).
+//
+// The cut is 7, 6 | 6, 5, 5, 6 | 6, 7 and not 7, 7 | 5, 5, 5, 5 | 7, 7, whose
+// busiest SIMD carries fewer rows (86 against 89 row-sweeps per block, 96
+// before): measured, a sweep costs about 80 cycles per row of the longest wave
+// and about 70 per row of the busiest SIMD, so the seven-row m bands gave back
+// what the lighter SIMDs gained (profiles/r07_trapezoid_ab.txt).
+constexpr int kTrapT = 8, kTrapR = 32, kTrapRowsMax = 7;
+constexpr int trap_h(int k) { return (k == 0 || k == 3 || k == 7) ? 7 : (k == 5) ? 5 : k == 6 ? 4 : 6; }
+constexpr int trap_d0(int k) { return k == 0 ? 8 : k == 1 ? 1 : k == 2 ? -4 : k == 3 ? 2 : 0; }
+constexpr int trap_ds(int k) { return (k == 0 || k == 1) ? -1 : (k == 2 || k == 3) ? 1 : 0; }
+constexpr int trap_dist(int k, int j) { return trap_d0(k) + trap_ds(k) * j < 0 ? 0 : trap_d0(k) + trap_ds(k) * j; }
+// is band row j (-1 / height: the neighbouring band's adjacent row) computed at
+// sweep I = 1 .. T of a block (I == 0: nothing skipped)?
+constexpr bool trap_live(int k, int j, int I) { return I == 0 || trap_dist(k, j) <= kTrapT - I; }
+// Bands of a tile in row order, by tile kind (0: top edge, 40 rows = 32 owned +
+// 8 ghost; 1: interior, 8 + 32 + 8; 2: bottom edge, 8 + 32): an interior tile
+// is cut 7, 6 | 6, 5, 5, 6 | 6, 7; an edge tile holds only its 40 live rows, the
+// 27 owned ones outside its (m, g) pair as 5, 4 | 5, 4 | 5, 4.
+constexpr int trap_kind(int tk, int b) {
+  if (tk == 0) return b == 6 ? 2 : b == 7 ? 3 : b % 2 == 0 ? 5 : 6;
+  if (tk == 1) return b == 0 ? 0 : b == 1 ? 1 : b == 6 ? 2 : b == 7 ? 3 : (b == 2 || b == 5) ? 4 : 5;
+  return b == 0 ? 0 : b == 1 ? 1 : b % 2 == 0 ? 5 : 6;
+}
+constexpr int trap_first(int tk, int b) {
+  int f = 0;
+  for (int q = 0; q < b; ++q) f += trap_h(trap_kind(tk, q));
+  return f;
+}
+// Band of wave w.  Waves w and w + 4 share a SIMD, and a sweep ends at the
+// per-sweep barrier, i.e. at the busiest SIMD: each (g, m) pair sits on one
+// SIMD (12, 11, .. 5 live rows over a block's sweeps), the other bands two per
+// SIMD (11, edge tiles 9).  (The pairing w, w + 1 measured 5 % slower:
+// DESIGN.md section 5.)
+constexpr int trap_band_of_wave(int w) {
+  return w == 0 ? 0 : w == 4 ? 1 : w == 1 ? 7 : w == 5 ? 6 : w == 2 ? 2 : w == 6 ? 3 : w == 3 ? 4 : 5;
+}
+constexpr int trap_tile_rows(int tk) { return tk == 1 ? 48 : 40; }
+constexpr int trap_own0(int tk) { return tk == 0 ? 0 : 8; }
+// does some owned row's block-end value depend on tile row `row` after sweep I?
+// (each sweep carries a value one row up and down)
+constexpr bool trap_needed(int tk, int row, int I) {
+  for (int r = trap_own0(tk); r < trap_own0(tk) + kTrapR; ++r)
+    if ((r > row ? r - row : row - r) <= kTrapT - I) return true;
+  return false;
+}
+constexpr bool trap_table_ok() {
+  for (int tk = 0; tk < 3; ++tk) {
+    int seen = 0;
+    for (int w = 0; w < 8; ++w) seen |= 1 << trap_band_of_wave(w);
+    if (seen != 0xFF) return false;  // every band on exactly one wave
+    // bands are contiguous from row 0 by construction: every row in exactly one band
+    if (trap_first(tk, 8) != trap_tile_rows(tk)) return false;
+    for (int b = 0; b < 8; ++b) {
+      const int k = trap_kind(tk, b), f = trap_first(tk, b);
+      if (trap_h(k) > kTrapRowsMax || trap_h(k) < 3) return false;
+      for (int I = 1; I <= kTrapT; ++I)
+        for (int j = -1; j <= trap_h(k); ++j) {  // the band's rows and the neighbouring bands' adjacent rows
+          const int row = f + j;
+          if (row < 0 || row >= trap_tile_rows(tk)) continue;
+          if (trap_live(k, j, I) != trap_needed(tk, row, I)) return false;
+        }
+    }
+  }
+  return true;
+}
+// live rows at sweep I on the busiest SIMD (waves s and s + 4)
+constexpr int trap_simd_rows(int tk, int I) {
+  int mx = 0;
+  for (int s = 0; s < 4; ++s) {
+    int n = 0;
+    for (int w = s; w < 8; w += 4) {
+      const int k = trap_kind(tk, trap_band_of_wave(w));
+      for (int j = 0; j < trap_h(k); ++j) n += trap_live(k, j, I) ? 1 : 0;
+    }
+    mx = n > mx ? n : mx;
+  }
+  return mx;
+}
+constexpr bool trap_simd_ok() {
+  constexpr int want[kTrapT] = {12, 11, 11, 11, 11, 11, 11, 11};
+  for (int I = 1; I <= kTrapT; ++I) {
+    if (trap_simd_rows(1, I) != want[I - 1]) return false;
+    if (trap_simd_rows(0, I) > want[I - 1] || trap_simd_rows(2, I) > want[I - 1]) return false;  // edge tiles never slower
+  }
+  return true;
+}
+static_assert(trap_table_ok(), "trapezoid bands: a row is computed at sweep I exactly when an owned row depends on it");
+static_assert(trap_simd_ok(), "trapezoid bands: busiest SIMD carries 12, 11, 11, 11, 11, 11, 11, 11 rows");
+
 //
 // COLS (LAY == 2; widths 64 / 128): the pair layout turned into column
 // strips.  Lane cp of band bb (W / 2 lanes per band, NT / (W / 2) bands) holds
@@ -131,6 +237,10 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   // full bookkeeping when some sweep is left unproven).
   constexpr bool kProof = MODE == kModeFwd && COLS;
   constexpr int kProofRow = RW / 2;
+  // Trapezoid schedule (see above): compiled into config 3's backward
+  // instantiation, taken when the plan is the one it is cut for (`trap` below).
+  constexpr bool kTrap = MODE == kModeBwd && LAY == 2 && WT == 128 && SPT == 12 && NT == 512;
+  constexpr int NS = kTrap ? 2 * kTrapRowsMax : SPT;     // register slots per lane
   // Column pairs, forward: the band edge rows' side neighbours come from LDS;
   // the backward and the quads use DPP moves (profiles/r05_ab_c3_sched.txt).
   constexpr bool kLdsSides = COLS && CPL == 2 && MODE == kModeFwd;
@@ -179,8 +289,27 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   const int pad = PAIR ? W : W + 1;  // pair layout keeps every pair 16-byte aligned
   const int blen = a.emax + 2 * pad;
   const int cp = COLS ? tid % HW : 0, bb = COLS ? tid / HW : 0;  // COLS: column group, band
-  // state index of register slot j
+  // trapezoid schedule: this wave's band (position in the tile, first row, kind); wave-uniform
+  const bool trap = kTrap && a.R == kTrapR && a.G == kTrapT && a.T == kTrapT && a.C >= 2 && H == a.C * kTrapR;
+  int tband = 0, tfirst = 0, tkind = 0, trows = 0;
+  if constexpr (kTrap) {
+    const int tk = tile == 0 ? 0 : tile == a.C - 1 ? 2 : 1;
+    tband = __builtin_amdgcn_readfirstlane(trap_band_of_wave(bb));
+    tfirst = __builtin_amdgcn_readfirstlane(trap_first(tk, tband));
+    tkind = __builtin_amdgcn_readfirstlane(trap_kind(tk, tband));
+    trows = __builtin_amdgcn_readfirstlane(trap_h(tkind));
+  }
+  // does register slot j hold a state?  (Only the trapezoid instantiation has
+  // spare slots: bands lower than kTrapRowsMax, and slots SPT.. of other plans.)
+  auto slot_ok = [&](int j) {
+    if constexpr (kTrap) return trap ? j / CPL < trows : j < SPT;
+    return true;
+  };
+  // state index of register slot j (meaningful where slot_ok(j))
   auto slot_state = [&](int j) {
+    if constexpr (kTrap) {
+      if (trap) return (tfirst + j / CPL) * W + CPL * cp + j % CPL;
+    }
     if (COLS) return (bb * RW + j / CPL) * W + CPL * cp + j % CPL;
     return PAIR ? 2 * (tid + (j >> 1) * NT) + (j & 1) : tid + j * NT;
   };
@@ -209,13 +338,13 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   }
 
   // ---- per-state constants into registers --------------------------------
-  double w[CW ? 1 : SPT][kStencilK];  // forward: gather weights; backward: reward-folded weights
+  double w[CW ? 1 : NS][kStencilK];  // forward: gather weights; backward: reward-folded weights
   double wc[CW ? SPT : 1][3];         // CW: w_x (both horizontal neighbours), w_+y, w_-y
   double edge_w[CW ? 2 * RW : 1];     // CW: per band row, w_0 of columns 0 / CPL-1 (x-border lanes, border rows; else 0)
   double c0[MODE == kModeFwd ? SPT : 1];  // forward: p0
   const size_t wbase = iS * kStencilK;
 #pragma unroll
-  for (int j = 0; j < SPT; ++j) {
+  for (int j = 0; j < NS; ++j) {
     const int l = slot_state(j);
     if (MODE == kModeFwd) c0[MODE == kModeFwd ? j : 0] = 0.0;
     if constexpr (CW) {
@@ -233,7 +362,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     } else {
 #pragma unroll
       for (int k = 0; k < kStencilK; ++k) w[j][k] = 0.0;
-      if (l < E) {
+      if (slot_ok(j) && l < E) {
         const int s = base + l;
         if (MODE == kModeFwd) c0[MODE == kModeFwd ? j : 0] = a.vin[iS + s];
 #pragma unroll
@@ -294,29 +423,29 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   }
   if (tid < 3) red[tid] = 0ull;
   if (tid == 0) lflag[0] = 0;
-  double cv[PAIR ? SPT : 1];  // pair layout: this thread's states, kept across sweeps
+  double cv[PAIR ? NS : 1];  // pair layout: this thread's states, kept across sweeps
 #pragma unroll
-  for (int j = 0; j < (PAIR ? SPT : 1); ++j) {
+  for (int j = 0; j < (PAIR ? NS : 1); ++j) {
     const int l = slot_state(j);
-    cv[j] = (PAIR && MODE == kModeBwd && l < E) ? (a.term[iS + base + l] ? 1.0 : 0.0) : 0.0;
+    cv[j] = (PAIR && MODE == kModeBwd && slot_ok(j) && l < E) ? (a.term[iS + base + l] ? 1.0 : 0.0) : 0.0;
   }
   // reload the register copy from an LDS buffer (after a ghost refresh or a rollback)
   auto reload = [&](const double* buf) {
     if (PAIR) {
 #pragma unroll
-      for (int j = 0; j < (PAIR ? SPT : 1); ++j) cv[j] = buf[pad + slot_state(j)];
+      for (int j = 0; j < (PAIR ? NS : 1); ++j) cv[j] = buf[pad + slot_state(j)];
     }
   };
 
   // per-slot predicates as bit masks (bit j: register slot j)
   unsigned own_bits = 0, pub_bits = 0, ext_bits = 0;
 #pragma unroll
-  for (int j = 0; j < SPT; ++j) {
+  for (int j = 0; j < NS; ++j) {
     const int l = slot_state(j);
-    const bool own = l >= own0 && l < own1;
+    const bool ok = slot_ok(j), own = ok && l >= own0 && l < own1;
     own_bits |= (own ? 1u : 0u) << j;
-    ext_bits |= (l < E ? 1u : 0u) << j;
-    pub_bits |= (((l >= own0 && l < pubA1) || (l >= pubB0 && l < own1)) ? 1u : 0u) << j;
+    ext_bits |= (ok && l < E ? 1u : 0u) << j;
+    pub_bits |= ((ok && ((l >= own0 && l < pubA1) || (l >= pubB0 && l < own1))) ? 1u : 0u) << j;
   }
 
   // Opaque per use, so the compiler does not hoist per-slot SGPR masks out of
@@ -438,7 +567,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   // COLS sweep between two register arrays (src -> dst): no register copies for
   // the old values the neighbouring rows still need; callers alternate the
   // arrays, two sweeps per loop iteration.
-  double cw[COLS ? SPT : 1];
+  double cw[COLS ? NS : 1];
   // band edge row e (0: top, 1: bottom) of band slot `band` (0 and NB + 1 are
   // the zero bands) in parity buffer `par`
   auto bnd_at = [&](int par, int band, int e) { return bnd + ((((size_t)par * (NB + 2) + band) * 2 + e) * HW + cp) * QW; };
@@ -450,7 +579,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   // fulltag (std::integral_constant<bool, FULL>): the forward's owned-delta
   // bookkeeping on every owned slot (FULL) or only on the slots of band row
   // kProofRow, the cheap proof of "not converged" (see the block loop).
-  auto cols_sweep = [&](const double (&src)[COLS ? SPT : 1], double (&dst)[COLS ? SPT : 1], int i,
+  auto cols_sweep = [&](const double (&src)[COLS ? NS : 1], double (&dst)[COLS ? NS : 1], int i,
                         unsigned& flags, auto p0tag, auto fulltag) {
     constexpr bool kP0 = decltype(p0tag)::value;
     constexpr bool kFull = decltype(fulltag)::value;
@@ -625,6 +754,102 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     }
   };
 
+  // Trapezoid schedule: one sweep of a band of kind K (ktag) from src to dst.
+  // I (itag) = 1 .. kTrapT: the sweep's place in a full block -- the rows to
+  // compute, the band edges to store and to read are compile-time sets; I = 0:
+  // nothing skipped.  `par`: parity buffer of the band-edge array.  The order is
+  // cols_sweep's for config 3's backward: band-edge stores, the rows with both
+  // vertical neighbours in registers, the barrier, then the band's bottom and
+  // top rows; the FMA chain is cols_sweep's, operand for operand.  A band edge is
+  // stored when the neighbouring band computes its adjacent row in this sweep
+  // (it is then exact: live in the sweep before), and read when the band's own
+  // edge row is computed.  No branch inside the sweep.
+  auto trap_sweep = [&](const double (&src)[COLS ? NS : 1], double (&dst)[COLS ? NS : 1], auto ktag, auto itag,
+                        const int par) {
+    if constexpr (kTrap) {
+      constexpr int K = decltype(ktag)::value, I = decltype(itag)::value, HB = trap_h(K);
+      constexpr bool top_live = trap_live(K, 0, I), bot_live = trap_live(K, HB - 1, I);
+      if constexpr (trap_live(K, -1, I)) *bnd_at(par, tband + 1, 0) = make_double2(src[0], src[1]);
+      if constexpr (trap_live(K, HB, I)) *bnd_at(par, tband + 1, 1) = make_double2(src[2 * HB - 2], src[2 * HB - 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      double above[2] = {0.0, 0.0}, below[2] = {0.0, 0.0};
+      auto rows = [&](int j1, int j2) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (h == 1 && j2 == j1) break;
+          const int jr = h == 0 ? j1 : j2;
+          const double* v = src + jr * 2;
+          const double* up = jr == 0 ? above : src + (jr > 0 ? jr - 1 : 0) * 2;
+          const double* dn = jr == HB - 1 ? below : src + (jr + 1 < HB ? jr + 1 : HB - 1) * 2;
+          const double lft = dpp_shift_f64<0x138>(v[1]);  // wave_shr1: left of column 0
+          const double rgt = dpp_shift_f64<0x130>(v[0]);  // wave_shl1: right of column 1
+          double acc[2];
+#pragma unroll
+          for (int c = 0; c < 2; ++c) acc[c] = fma(w[CW ? 0 : jr * 2 + c][0], v[c], 0.0);
+          acc[0] = fma(w[CW ? 0 : jr * 2][1], v[1], acc[0]);
+          acc[1] = fma(w[CW ? 0 : jr * 2 + 1][1], rgt, acc[1]);
+          acc[0] = fma(w[CW ? 0 : jr * 2][2], lft, acc[0]);
+          acc[1] = fma(w[CW ? 0 : jr * 2 + 1][2], v[0], acc[1]);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) acc[c] = fma(w[CW ? 0 : jr * 2 + c][3], dn[c], acc[c]);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) acc[c] = fma(w[CW ? 0 : jr * 2 + c][4], up[c], acc[c]);
+          dst[jr * 2] = acc[0];
+          dst[jr * 2 + 1] = acc[1];
+        }
+      };
+      // rows 1 .. HB - 2 that are computed in this sweep: a contiguous range
+      // (the ghost distance is monotone along a band), two rows at a time
+      constexpr int lo = [] { int j = 1; while (j <= HB - 2 && !trap_live(K, j, I)) ++j; return j; }();
+      constexpr int hi = [] { int j = HB - 2; while (j >= 1 && !trap_live(K, j, I)) --j; return j; }();
+#pragma unroll
+      for (int j = lo; j <= hi; j += 2) rows(j, j + 1 <= hi ? j + 1 : j);
+      __syncthreads();
+      if constexpr (top_live) {
+        const double2 x = *bnd_at(par, tband, 1);
+        above[0] = x.x; above[1] = x.y;
+      }
+      if constexpr (bot_live) {
+        const double2 y = *bnd_at(par, tband + 2, 0);
+        below[0] = y.x; below[1] = y.y;
+      }
+      if constexpr (top_live && bot_live) rows(HB - 1, 0);
+      else if constexpr (bot_live) rows(HB - 1, HB - 1);
+      else if constexpr (top_live) rows(0, 0);
+    }
+  };
+  // a block's Tm sweeps for a band of kind K: a full block unrolled with its
+  // per-sweep row sets, any other length (and a.trap_noskip) with every row
+  // swept (kind NK: the band's height only)
+  auto trap_block = [&](auto ktag, auto nktag, const int Tm) {
+    if constexpr (kTrap) {
+      using std::integral_constant;
+      if (Tm == kTrapT && !a.trap_noskip) {
+        trap_sweep(cv, cw, ktag, integral_constant<int, 1>{}, 0);
+        trap_sweep(cw, cv, ktag, integral_constant<int, 2>{}, 1);
+        trap_sweep(cv, cw, ktag, integral_constant<int, 3>{}, 0);
+        trap_sweep(cw, cv, ktag, integral_constant<int, 4>{}, 1);
+        trap_sweep(cv, cw, ktag, integral_constant<int, 5>{}, 0);
+        trap_sweep(cw, cv, ktag, integral_constant<int, 6>{}, 1);
+        trap_sweep(cv, cw, ktag, integral_constant<int, 7>{}, 0);
+        trap_sweep(cw, cv, ktag, integral_constant<int, 8>{}, 1);
+      } else {
+        constexpr int HB = trap_h(decltype(nktag)::value);
+        const std::integral_constant<int, 0> all{};
+        int i = 0;
+        for (; i + 1 < Tm; i += 2) {
+          trap_sweep(cv, cw, nktag, all, 0);
+          trap_sweep(cw, cv, nktag, all, 1);
+        }
+        if (i < Tm) {
+          trap_sweep(cv, cw, nktag, all, 0);
+#pragma unroll
+          for (int j = 0; j < 2 * HB; ++j) cv[j] = cw[j];
+        }
+      }
+    }
+  };
+
   // Halo exchange in tagged granules (cluster.h): this instance's region of
   // a.gran is [2 parities][H rows][W] x 16 B plus pads (cluster.h), of a.sgran [kSumRows][H tiles] x 16 B
   // (summaries by block % kSumSlots, then the XCC ids and the full forward flags).
@@ -755,15 +980,30 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     double mxd = 0.0;
     if constexpr (COLS) {
       if constexpr (MODE == kModeBwd) {
-        int i = 0;
-        for (; i + 1 < Tm; i += 2) {
-          cols_sweep(cv, cw, i, flags, std::false_type{}, std::true_type{});
-          cols_sweep(cw, cv, i + 1, flags, std::false_type{}, std::true_type{});
-        }
-        if (i < Tm) {
-          cols_sweep(cv, cw, i, flags, std::false_type{}, std::true_type{});
+        if (kTrap && trap) {
+          // trapezoid schedule: one wave-uniform branch on the band kind around
+          // the whole block, each sweep a straight-line block
+          using std::integral_constant;
+          switch (tkind) {
+            case 0: trap_block(integral_constant<int, 0>{}, integral_constant<int, 7>{}, Tm); break;
+            case 1: trap_block(integral_constant<int, 1>{}, integral_constant<int, 4>{}, Tm); break;
+            case 2: trap_block(integral_constant<int, 2>{}, integral_constant<int, 4>{}, Tm); break;
+            case 3: trap_block(integral_constant<int, 3>{}, integral_constant<int, 7>{}, Tm); break;
+            case 4: trap_block(integral_constant<int, 4>{}, integral_constant<int, 4>{}, Tm); break;
+            case 5: trap_block(integral_constant<int, 5>{}, integral_constant<int, 5>{}, Tm); break;
+            default: trap_block(integral_constant<int, 6>{}, integral_constant<int, 6>{}, Tm); break;
+          }
+        } else {
+          int i = 0;
+          for (; i + 1 < Tm; i += 2) {
+            cols_sweep(cv, cw, i, flags, std::false_type{}, std::true_type{});
+            cols_sweep(cw, cv, i + 1, flags, std::false_type{}, std::true_type{});
+          }
+          if (i < Tm) {
+            cols_sweep(cv, cw, i, flags, std::false_type{}, std::true_type{});
 #pragma unroll
-          for (int j = 0; j < (COLS ? SPT : 1); ++j) cv[j] = cw[j];
+            for (int j = 0; j < (COLS ? SPT : 1); ++j) cv[j] = cw[j];
+          }
         }
       } else {
         // forward: the p0 add only in waves holding a nonzero p0 (the start states:
@@ -791,7 +1031,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     if (resc) {  // owned maximum of the block's last sweep (fmax: a NaN is skipped, inf kept)
       const unsigned ob = slot_bits(own_bits);
 #pragma unroll
-      for (int j = 0; j < SPT; ++j)
+      for (int j = 0; j < NS; ++j)
         if ((ob >> j) & 1u) mxd = fmax(mxd, fabs(PAIR ? cv[PAIR ? j : 0] : cur[pad + slot_state(j)]));
     }
     stamp(0);
@@ -815,7 +1055,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
       // the stores spread over all waves after the barrier below.
       const unsigned pb = slot_bits(pub_bits);
 #pragma unroll
-      for (int jp = 0; jp < SPT / 2; ++jp)
+      for (int jp = 0; jp < NS / 2; ++jp)
         if ((pb >> (2 * jp)) & 1u)
           *reinterpret_cast<double2*>(cur + pad + slot_state(2 * jp)) =
               make_double2(cv[PAIR ? 2 * jp : 0], cv[PAIR ? 2 * jp + 1 : 0]);
@@ -1006,7 +1246,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     if constexpr (PAIR) {
       const unsigned ob = slot_bits(own_bits), xb = slot_bits(ext_bits);
 #pragma unroll
-      for (int jp = 0; jp < SPT / 2; ++jp) {  // pairs: own / ext predicates hold for both states
+      for (int jp = 0; jp < NS / 2; ++jp) {  // pairs: own / ext predicates hold for both states
         const int l = slot_state(2 * jp);
         const bool own = (ob >> (2 * jp)) & 1u, ext = (xb >> (2 * jp)) & 1u;
         double2 v = make_double2(cv[PAIR ? 2 * jp : 0], cv[PAIR ? 2 * jp + 1 : 0]);
@@ -1045,7 +1285,7 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     if (COLS) {  // the register state into the LDS tile for the final per-action sweep
       const unsigned xb = slot_bits(ext_bits);
 #pragma unroll
-      for (int jp = 0; jp < SPT / 2; ++jp)
+      for (int jp = 0; jp < NS / 2; ++jp)
         if ((xb >> (2 * jp)) & 1u)
           *reinterpret_cast<double2*>(cur + pad + slot_state(2 * jp)) = make_double2(cv[PAIR ? 2 * jp : 0], cv[PAIR ? 2 * jp + 1 : 0]);
       if constexpr (CW) {
@@ -1394,6 +1634,7 @@ int cluster_run(int mode, const ClusterPlan& plan, ClusterArgs a, int B, hipStre
   a.test_drop = tk.drop;
   a.gather_ticks = tk.gather_ticks;
   a.eager_summary = env_int("IRLMX_EAGER_SUMMARY", 0) ? 1 : 0;
+  a.trap_noskip = env_int("IRLMX_TRAP_NOSKIP", 0) ? 1 : 0;
   for (int b0 = 0; b0 < B; b0 += p.per_launch) {
     const int nb = std::min(p.per_launch, B - b0);
     a.b0 = b0;
