@@ -176,6 +176,28 @@ int irlmx_backward_maxent(const irlmx_mdp* mdp, const double* reward, const uint
                           size_t workspace_bytes, void* stream);
 
 /*
+ * The same backward pass with one exponent per state (no reference counterpart
+ * beyond maxent.py:119-159 itself): every partition value is held as
+ * m * 2^e, m a float64 in [0.5, 1) or 0 and e an int32, so the policy stays
+ * finite -- and right -- where the partition vector spans more than float64's
+ * exponent range and irlmx_backward_maxent, which keeps one scale per
+ * instance, returns NaN rows and wrong finite rows beside them (a reward
+ * contrast of 4 on a grid 256 wide is enough).  Same weights, slot order and
+ * fused multiply-adds as irlmx_backward_maxent: bit-identical to it (rescale
+ * != 0) wherever that pass neither underflows nor overflows.  Exactly 2*S
+ * sweeps; fully asynchronous on `stream`.  Non-finite exp(reward) gives an
+ * all-NaN policy for that instance; a state that cannot reach a terminal 0 / 0
+ * = NaN, as in the reference.  STENCIL5 and ELL layouts, S <= 2^19;
+ * IRLMX_EINVAL for DENSE.  Workspace: irlmx_workspace_bytes(mdp,
+ * IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE).  Models above 4096 states
+ * run one launch per sweep (2*S - 1 launches: correct, and slow at config-4
+ * size); there is no persistent multi-CU form of this pass.
+ */
+int irlmx_backward_maxent_extended(const irlmx_mdp* mdp, const double* reward, const uint8_t* terminal,
+                                   double* p_action, int32_t* status, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
+/*
  * The same backward pass in numpy's own floating-point order (no reference
  * counterpart beyond maxent.py:142-159 itself): every p[a].dot(zs) summed as
  * numpy's OpenBLAS dgemv_t sums it on a Haswell-family x86-64 host (lane
@@ -295,6 +317,9 @@ int irlmx_value_iteration_numpy_order(const irlmx_mdp* mdp, const double* reward
                                     VI: actions compiled per state; values exchanged per sweep */
 #define IRLMX_PLAN_NO_RESCALE 0x100 /* OR into op (IRLMX_OP_BACKWARD only): the plan of a rescale = 0 call, which
                                       never takes the cluster shape (its overflow bookkeeping is per sweep) */
+#define IRLMX_PLAN_EXTENDED_RANGE 0x200 /* OR into op (IRLMX_OP_BACKWARD only, here and in irlmx_workspace_bytes):
+                                          irlmx_backward_maxent_extended -- shape fused or sweep, [5], [7], [8]
+                                          (sweep: the 2*S - 1 sweep launches) and [9] */
 int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* plan);
 
 /*

@@ -1,0 +1,384 @@
+// Extended-range MaxEnt backward pass (irlmx_backward_maxent_extended) on gfx950.
+//
+// The rescaled backward (fixed_point.hip, cluster.hip) keeps ONE power-of-two
+// scale per instance, so the partition vector zs must fit float64's exponent
+// range under a common scale.  A reward contrast of 4 along a grid 256 wide
+// already spreads zs over more than 2^2098: the far states flush to 0, their
+// policy rows are 0 / 0, and the rows beside the underflow front are finite
+// and wrong ("Extended range").
+//
+// Here every partition value carries its own exponent:
+//
+//   z(s) = m(s) * 2^e(s),  m in [0.5, 1) or exactly 0 (frexp's form), e an int32,
+//                          kExtZero for an exact zero
+//
+// and one collapsed sweep over the weights of bwd_weights_kernel is
+//
+//   E        = max e(nb_k) over the slots k with w_k != 0
+//   acc      = fma(w_k, ldexp(m(nb_k), e(nb_k) - E), acc)   in slot order
+//   (m', d)  = frexp(acc),  e' = E + d                      (acc == 0: zero)
+//
+// Slot order and the explicit fma are those of bwd_fused_kernel /
+// bwd_sweep_kernel, and scaling every operand of an fma chain by one power of
+// two commutes with rounding while nothing is subnormal: wherever the rescaled
+// pass neither underflows nor overflows, this pass returns the same bits.
+// There is no rescaling, no per-sweep maximum and no convergence test; the
+// sweep count is the reference's 2*S (maxent.py:154), the last one per action.
+//
+// Two shapes: fused (one workgroup per instance, mantissas and exponents
+// ping-pong in LDS, 24 B per state, one barrier per sweep) and per sweep (one
+// launch per sweep over all instances, buffers in the caller's workspace; the
+// launch count is fixed, so the host never polls).
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+
+#include "common.h"
+#include "fixed_point.h"
+
+namespace irlmx {
+
+constexpr int kExtZero = INT_MIN;      // exponent of an exact zero: never raises a maximum
+constexpr int kExtMinShift = -1100;    // ldexp(m, shift) is 0 below -1075 already
+constexpr int kExtMaxStates = 1 << 19; // |e| grows by < 1100 per sweep: no int32 wrap within 2*S sweeps
+constexpr size_t kExtLdsPerState = 2 * sizeof(double) + 2 * sizeof(int);
+constexpr size_t kExtLdsMax = 160 * 1024;
+
+struct ExtArgs {
+  Model m;
+  const double* w;  // [B][K][S] collapsed, reward-folded weights (bwd_weights_kernel)
+  const double* reward;
+  const uint8_t* term;
+  const int32_t* bad;  // [B] non-finite weights (bwd_nonfinite_rule)
+  double* pi;          // [B][S][A]
+  int32_t* status;
+};
+
+struct ExtWs {
+  double* wgt;     // [B][K][S]
+  int32_t* bad;    // [B]
+  double* man[2];  // [B][S] mantissas, ping and pong (per-sweep shape)
+  int32_t* exp[2]; // [B][S] exponents
+  size_t total;
+};
+
+// m * 2^(e - E) with the shift clamped to [kExtMinShift, 0]: the difference is
+// taken in 64 bits (e and E may be far apart, or kExtZero).  A slot whose
+// weight is 0 may hold e > E; its product is 0 at any finite shift.
+__device__ inline double ext_aligned(double mant, int e, int E) {
+  const long long d = (long long)e - (long long)E;
+  const int sh = d < kExtMinShift ? kExtMinShift : (d > 0 ? 0 : (int)d);
+  return ldexp(mant, sh);
+}
+
+// acc -> (mantissa, exponent) on top of the alignment exponent E
+__device__ inline void ext_split(double acc, int E, double* mant, int* e) {
+  if (acc == 0.0) { *mant = 0.0; *e = kExtZero; return; }
+  if (!isfinite(acc)) { *mant = acc; *e = 0; return; }  // non-finite weights: the instance is NaN-filled
+  int d;
+  *mant = frexp(acc, &d);
+  *e = E + d;
+}
+
+__device__ inline void ext_init_state(bool terminal, double* mant, int* e) {
+  *mant = terminal ? 0.5 : 0.0;  // 1 = 0.5 * 2^1
+  *e = terminal ? 1 : kExtZero;
+}
+
+// The last sweep, per action (maxent.py:155-159): every action of a state is
+// aligned to the same E, za = er * acc rounded, the sequential action sum, and
+// za / zsum, in which the common 2^E cancels.
+__device__ inline void ext_policy_row(const ExtArgs& a, int b, int s, const double* zm, const int* ze) {
+  const Model& m = a.m;
+  const int K = m.K, A = m.A;
+  double* out = a.pi + ((size_t)b * m.S + s) * A;
+  int E = kExtZero;
+  for (int k = 0; k < K; ++k) {
+    bool any = false;
+    for (int act = 0; act < A; ++act) any |= row_val(m, b, act, k, s) != 0.0;
+    if (any) E = max(E, ze[row_nbr(m, b, s, k)]);
+  }
+  const double er = exp(a.reward[(size_t)b * m.S + s]);
+  double za[kMaxActions];
+  double zsum = 0.0;
+  for (int act = 0; act < A; ++act) {
+    double acc = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const int n = row_nbr(m, b, s, k);
+      acc = fma(row_val(m, b, act, k, s), ext_aligned(zm[n], ze[n], E), acc);
+    }
+    za[act] = __dmul_rn(er, acc);  // rounded product, then the sum (maxent.py:155-156)
+    zsum = __dadd_rn(zsum, za[act]);
+  }
+  for (int act = 0; act < A; ++act) out[act] = za[act] / zsum;
+}
+
+__device__ inline void ext_nan_row(const ExtArgs& a, int b, int s) {
+  double* out = a.pi + ((size_t)b * a.m.S + s) * a.m.A;
+  for (int act = 0; act < a.m.A; ++act) out[act] = kNaN;
+}
+
+// ---------------------------------------------------------------------------
+// fused shape: one workgroup per instance for the whole loop
+// ---------------------------------------------------------------------------
+
+template <int SPT, int KMAX>
+__global__ void __launch_bounds__(1024) ext_fused_kernel(ExtArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ext_smem[];
+  const Model& m = a.m;
+  const int S = m.S, K = m.K;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  double* manA = (double*)ext_smem;
+  double* manB = manA + S;
+  int* expA = (int*)(manB + S);
+  int* expB = expA + S;
+
+  if (a.bad[b]) {  // bwd_nonfinite_rule: non-finite weights, NaN everywhere (uniform over the workgroup)
+    for (int s = tid; s < S; s += nt) ext_nan_row(a, b, s);
+    if (tid == 0) a.status[b] = IRLMX_OK;
+    return;
+  }
+
+  double w[SPT][KMAX];
+  int nb[SPT][KMAX];
+  const double* wb = a.w + (size_t)b * K * S;
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    const int s = tid + j * nt;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) { w[j][k] = 0.0; nb[j][k] = 0; }
+    if (s < S) {
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K) { w[j][k] = wb[(size_t)k * S + s]; nb[j][k] = row_nbr(m, b, s, k); }
+    }
+  }
+  for (int s = tid; s < S; s += nt) ext_init_state(a.term[(size_t)b * S + s] != 0, &manA[s], &expA[s]);
+  __syncthreads();
+
+  // 2*S sweeps in all (maxent.py:154): the first 2*S - 1 on the action-summed
+  // table, the last one per action because it also produces za.
+  const long long collapsed = 2LL * S - 1;
+  for (long long it = 0; it < collapsed; ++it) {
+    const double* min_ = (it & 1) ? manB : manA;
+    const int* ein = (it & 1) ? expB : expA;
+    double* mout = (it & 1) ? manA : manB;
+    int* eout = (it & 1) ? expA : expB;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      const int s = tid + j * nt;
+      if (s < S) {
+        int E = kExtZero;
+        double acc = 0.0;
+        if constexpr (KMAX <= 8) {  // neighbours read once, held in registers
+          double zm[KMAX];
+          int ze[KMAX];
+#pragma unroll
+          for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+              zm[k] = min_[nb[j][k]];
+              ze[k] = ein[nb[j][k]];
+              if (w[j][k] != 0.0) E = max(E, ze[k]);
+            }
+#pragma unroll
+          for (int k = 0; k < KMAX; ++k)
+            if (k < K) acc = fma(w[j][k], ext_aligned(zm[k], ze[k], E), acc);
+        } else {  // many slots: the exponents are read twice instead (registers)
+#pragma unroll
+          for (int k = 0; k < KMAX; ++k)
+            if (k < K && w[j][k] != 0.0) E = max(E, ein[nb[j][k]]);
+#pragma unroll
+          for (int k = 0; k < KMAX; ++k)
+            if (k < K) acc = fma(w[j][k], ext_aligned(min_[nb[j][k]], ein[nb[j][k]], E), acc);
+        }
+        ext_split(acc, E, &mout[s], &eout[s]);
+      }
+    }
+    __syncthreads();
+  }
+  const double* zm = (collapsed & 1) ? manB : manA;
+  const int* ze = (collapsed & 1) ? expB : expA;
+  for (int s = tid; s < S; s += nt) ext_policy_row(a, b, s, zm, ze);
+  if (tid == 0) a.status[b] = IRLMX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// per-sweep shape: one launch per sweep over all instances
+// ---------------------------------------------------------------------------
+
+__global__ void ext_init_kernel(ExtArgs a, ExtWs ws) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  if (s >= a.m.S) return;
+  const size_t i = (size_t)b * a.m.S + s;
+  ext_init_state(a.term[i] != 0, &ws.man[0][i], &ws.exp[0][i]);
+}
+
+__global__ void __launch_bounds__(kSweepThreads) ext_sweep_kernel(ExtArgs a, ExtWs ws, int odd) {
+  const Model& m = a.m;
+  const int S = m.S, K = m.K;
+  const int b = blockIdx.y;
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const double* min_ = ws.man[odd] + (size_t)b * S;
+  const int* ein = ws.exp[odd] + (size_t)b * S;
+  const double* wb = a.w + (size_t)b * K * S;
+  int E = kExtZero;
+  for (int k = 0; k < K; ++k)
+    if (wb[(size_t)k * S + s] != 0.0) E = max(E, ein[row_nbr(m, b, s, k)]);
+  double acc = 0.0;
+  for (int k = 0; k < K; ++k) {
+    const int n = row_nbr(m, b, s, k);
+    acc = fma(wb[(size_t)k * S + s], ext_aligned(min_[n], ein[n], E), acc);
+  }
+  const size_t o = (size_t)b * S + s;
+  ext_split(acc, E, &ws.man[odd ^ 1][o], &ws.exp[odd ^ 1][o]);
+}
+
+__global__ void __launch_bounds__(kSweepThreads) ext_final_kernel(ExtArgs a, ExtWs ws, int odd) {
+  const int S = a.m.S;
+  const int b = blockIdx.y;
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  if (a.bad[b]) ext_nan_row(a, b, s);  // bwd_nonfinite_rule
+  else ext_policy_row(a, b, s, ws.man[odd] + (size_t)b * S, ws.exp[odd] + (size_t)b * S);
+  if (s == 0) a.status[b] = IRLMX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// host-side dispatch
+// ---------------------------------------------------------------------------
+
+// (SPT, KMAX) pairs instantiated: those of the ordinary fused backward; every
+// pair compiles without VGPR spills at __launch_bounds__(1024)
+// (tools/kernel_resources.py).
+static constexpr bool ext_pair_ok(int spt, int kmax) {
+  return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt <= 2) || (kmax == 32 && spt == 1);
+}
+
+template <int S_, int K_>
+static void (*ext_fused_ptr())(ExtArgs) {
+  if constexpr (ext_pair_ok(S_, K_)) return &ext_fused_kernel<S_, K_>;
+  else return nullptr;
+}
+
+static void (*ext_fused_fn(const FusedShape& f))(ExtArgs) {
+  const int s = f.spt, k = f.kmax;
+  if (s == 1 && k == 5) return ext_fused_ptr<1, 5>();
+  if (s == 2 && k == 5) return ext_fused_ptr<2, 5>();
+  if (s == 4 && k == 5) return ext_fused_ptr<4, 5>();
+  if (s == 1 && k == 8) return ext_fused_ptr<1, 8>();
+  if (s == 2 && k == 8) return ext_fused_ptr<2, 8>();
+  if (s == 1 && k == 16) return ext_fused_ptr<1, 16>();
+  if (s == 2 && k == 16) return ext_fused_ptr<2, 16>();
+  if (s == 1 && k == 32) return ext_fused_ptr<1, 32>();
+  return nullptr;
+}
+
+static size_t ext_fused_lds(const Model& m) { return (size_t)m.S * kExtLdsPerState; }
+
+// The fused shape of the extended pass: the ordinary fused backward's thread
+// layout at every width (there is no cluster form to prefer at 64 / 128), when
+// its registers (an instantiated pair) and LDS fit; else the per-sweep shape.
+static bool ext_fused_shape(const Model& m, FusedShape* out) {
+  if (!fused_shape(m, IRLMX_OP_BACKWARD, out, false)) return false;
+  return ext_pair_ok(out->spt, out->kmax) && ext_fused_lds(m) <= kExtLdsMax;
+}
+
+static ExtWs ext_carve(const Model& m, void* base) {
+  ExtWs w;
+  size_t off = 0;
+  char* p = (char*)base;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += align256(bytes);
+    return (void*)r;
+  };
+  const size_t B = m.B, S = m.S;
+  FusedShape fs;
+  const bool sweep = !ext_fused_shape(m, &fs);
+  w.wgt = (double*)take(B * m.K * S * sizeof(double));
+  w.bad = (int32_t*)take(B * sizeof(int32_t));
+  for (int i = 0; i < 2; ++i) w.man[i] = (double*)take(sweep ? B * S * sizeof(double) : 0);
+  for (int i = 0; i < 2; ++i) w.exp[i] = (int32_t*)take(sweep ? B * S * sizeof(int32_t) : 0);
+  w.total = off;
+  return w;
+}
+
+int extended_check_model(const Model& m, const char* fn) {
+  if (m.dense) {
+    set_error("%s: the extended-range backward does not run the DENSE layout (STENCIL5 and ELL only)", fn);
+    return IRLMX_EINVAL;
+  }
+  if (m.S > kExtMaxStates) {
+    set_error("%s: the extended-range backward takes at most %d states, got %d", fn, kExtMaxStates, m.S);
+    return IRLMX_EINVAL;
+  }
+  return 0;
+}
+
+size_t extended_workspace_bytes(const Model& m) { return ext_carve(m, nullptr).total; }
+
+void extended_plan(const Model& m, int64_t* plan) {
+  FusedShape fs;
+  if (ext_fused_shape(m, &fs)) {
+    plan[0] = IRLMX_SHAPE_FUSED;
+    plan[5] = fs.spt;
+    plan[7] = fs.threads;
+    plan[8] = 1;
+    plan[9] = (int64_t)ext_fused_lds(m);
+    return;
+  }
+  plan[0] = IRLMX_SHAPE_SWEEP;
+  plan[5] = 1;
+  plan[7] = kSweepThreads;
+  plan[8] = 2LL * m.S - 1;  // sweep launches (plus the weights, the start vector and the per-action sweep)
+}
+
+}  // namespace irlmx
+
+using namespace irlmx;
+
+extern "C" int irlmx_backward_maxent_extended(const irlmx_mdp* mdp, const double* reward, const uint8_t* terminal,
+                                              double* p_action, int32_t* status, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  if (int rc = validate(mdp)) return rc;
+  const Model m = make_model(mdp);
+  if (int rc = extended_check_model(m, "backward_maxent_extended")) return rc;
+  if (int rc = need_all("backward_maxent_extended",
+                        {{reward, "reward"}, {terminal, "terminal"}, {p_action, "p_action"}, {status, "status"}}))
+    return rc;
+  const size_t need = ext_carve(m, nullptr).total;
+  if (workspace_bytes < need || !workspace) {
+    set_error("workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    return IRLMX_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ExtWs ws = ext_carve(m, workspace);
+  hipError_t e = hipMemsetAsync(ws.bad, 0, (size_t)m.B * sizeof(int32_t), st);
+  if (e != hipSuccess) return hip_fail(e, "workspace memset");
+  bwd_weights_launch(m, reward, ws.wgt, ws.bad, st);
+  ExtArgs a{m, ws.wgt, reward, terminal, ws.bad, p_action, status};
+  FusedShape fs;
+  if (ext_fused_shape(m, &fs)) {
+    void (*kfn)(ExtArgs) = ext_fused_fn(fs);
+    if (!kfn) { set_error("no extended fused kernel for spt=%d kmax=%d", fs.spt, fs.kmax); return IRLMX_EINVAL; }
+    const size_t lds = ext_fused_lds(m);
+    e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
+    hipLaunchKernelGGL(kfn, dim3(m.B), dim3(fs.threads), lds, st, a);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "ext_fused_kernel");
+  }
+  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  count_event(IRLMX_CTR_SWEEP_CALLS);
+  hipLaunchKernelGGL(ext_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
+  const long long collapsed = 2LL * m.S - 1;
+  for (long long it = 0; it < collapsed; ++it)
+    hipLaunchKernelGGL(ext_sweep_kernel, g, dim3(kSweepThreads), 0, st, a, ws, (int)(it & 1));
+  hipLaunchKernelGGL(ext_final_kernel, g, dim3(kSweepThreads), 0, st, a, ws, (int)(collapsed & 1));
+  e = hipGetLastError();
+  return e == hipSuccess ? 0 : hip_fail(e, "extended backward");
+}

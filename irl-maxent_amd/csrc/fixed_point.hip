@@ -38,73 +38,17 @@
 #include "cluster.h"
 #include "common.h"
 #include "dense.h"
+#include "fixed_point.h"
 
 namespace irlmx {
 
-constexpr int kFusedMaxStates = 4096;
-
 // Largest S run by the fused shape; IRLMX_FUSED_MAX_STATES lowers it (tests use
 // 0 to drive every size through the sweep shape).
-static int fused_max_states() {
+int fused_max_states() {
   const char* e = getenv("IRLMX_FUSED_MAX_STATES");
   if (!e || !*e) return kFusedMaxStates;
   const int v = atoi(e);
   return v < kFusedMaxStates ? v : kFusedMaxStates;
-}
-constexpr int kMaxActions = 8;
-constexpr int kSweepThreads = 256;
-
-// ---------------------------------------------------------------------------
-// model views
-// ---------------------------------------------------------------------------
-
-struct Model {
-  int S, A, K, W, H, B, stencil, shared, Kc, dense;
-  int props;  // irlmx_mdp.props: IRLMX_PROPS_KNOWN | IRLMX_PROP_* from irlmx_mdp_properties, or 0 (unknown)
-  const double* row_val;
-  const int32_t* row_idx;
-  const int32_t* col_idx;
-  const double* col_val;
-};
-
-static Model make_model(const irlmx_mdp* m) {
-  Model o;
-  o.S = m->n_states;
-  o.A = m->n_actions;
-  o.stencil = m->layout == IRLMX_LAYOUT_STENCIL5;
-  o.dense = m->layout == IRLMX_LAYOUT_DENSE;
-  o.K = o.stencil ? kStencilK : (o.dense ? m->n_states : m->k_row);
-  o.Kc = o.stencil ? kStencilK : (o.dense ? m->n_states : m->k_col);
-  o.W = m->width;
-  o.H = m->height;
-  o.B = m->batch;
-  o.shared = m->shared != 0;
-  o.row_val = m->row_val;
-  o.row_idx = m->row_idx;
-  o.col_idx = m->col_idx;
-  o.col_val = m->col_val;
-  o.props = m->props;
-  return o;
-}
-
-__device__ inline size_t inst_of(const Model& m, int b) { return m.shared ? 0 : (size_t)b; }
-
-// neighbour (row form) of s in slot k
-__device__ inline int row_nbr(const Model& m, int b, int s, int k) {
-  if (m.stencil) return stencil_nbr(s, k, m.W, m.H);
-  const int t = m.row_idx[(inst_of(m, b) * m.K + k) * m.S + s];
-  return IRLMX_DCHECK(t >= 0 && t < m.S, kCheckIndex) ? t : s;
-}
-
-__device__ inline double row_val(const Model& m, int b, int a, int k, int s) {
-  return m.row_val[((inst_of(m, b) * m.A + a) * m.K + k) * m.S + s];
-}
-
-// source (column form) of target t in slot k
-__device__ inline int col_src(const Model& m, int b, int t, int k) {
-  if (m.stencil) return stencil_nbr(t, k, m.W, m.H);
-  const int s = m.col_idx[(inst_of(m, b) * m.Kc + k) * m.S + t];
-  return IRLMX_DCHECK(s >= 0 && s < m.S, kCheckIndex) ? s : t;
 }
 
 // ---------------------------------------------------------------------------
@@ -129,8 +73,6 @@ struct Ws {
   int* err;                   // [4]: error bits, rendezvous counters
   size_t total;
 };
-
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 static bool use_fused(const Model& m, int op);
 
@@ -263,6 +205,10 @@ __global__ void bwd_weights_kernel(Model m, const double* __restrict__ reward, d
   // non-finite weights make some partition value non-finite within two sweeps,
   // and the reference's dense product then NaN everywhere (bwd_nonfinite_rule)
   if (nf) atomicOr(&bad[b], 1);
+}
+
+void bwd_weights_launch(const Model& m, const double* reward, double* w, int32_t* bad, hipStream_t st) {
+  hipLaunchKernelGGL(bwd_weights_kernel, dim3((m.S + 255) / 256, m.B), dim3(256), 0, st, m, reward, w, bad);
 }
 
 // bwd_nonfinite_rule for the cluster shape: NaN policy for flagged instances
@@ -2229,12 +2175,6 @@ __global__ void fill_kernel(double* p, size_t n, double v) {
 // host-side dispatch
 // ---------------------------------------------------------------------------
 
-struct FusedShape {
-  int spt;
-  int kmax;
-  int threads;
-};
-
 static int pick_kmax(int K) {
   if (K <= 5) return 5;
   if (K <= 8) return 8;
@@ -2261,14 +2201,14 @@ static constexpr bool fused_pair_ok(int op, int spt, int kmax) {
   return false;
 }
 
-static bool fused_shape(const Model& m, int op, FusedShape* out) {
+bool fused_shape(const Model& m, int op, FusedShape* out, bool cluster_first) {
   if (m.dense || m.S > fused_max_states() || m.A > kMaxActions) return false;
   // Grids of width 64 / 128 run the forward and backward passes on the cluster
   // shape even when they fit one CU: its register-resident pair layouts sweep
   // 4-5x faster than the general-sparsity fused kernel, and a single instance
   // then spreads over several CUs (cluster.hip).
-  if ((op == IRLMX_OP_FORWARD || op == IRLMX_OP_BACKWARD) && m.stencil && (m.W == 64 || m.W == 128) &&
-      env_int("IRLMX_CLUSTER", 1) != 0)
+  if (cluster_first && (op == IRLMX_OP_FORWARD || op == IRLMX_OP_BACKWARD) && m.stencil &&
+      (m.W == 64 || m.W == 128) && env_int("IRLMX_CLUSTER", 1) != 0)
     return false;
   const int K = op == IRLMX_OP_FORWARD ? m.Kc : m.K;
   const int kmax = pick_kmax(K);
@@ -2326,7 +2266,7 @@ IRLMX_FUSED_GETTER(vi_fused_ptr, vi_fused_kernel, IRLMX_OP_VALUE_ITERATION, Soft
     if (_e != hipSuccess) return hip_fail(_e, #GETTER);                                               \
   } while (0)
 
-static int validate(const irlmx_mdp* mdp) {
+int validate(const irlmx_mdp* mdp) {
   if (!mdp) { set_error("mdp is NULL"); return IRLMX_EINVAL; }
   const Model m = make_model(mdp);
   if (m.S <= 0 || m.A <= 0 || m.B <= 0) { set_error("bad sizes S=%d A=%d B=%d", m.S, m.A, m.B); return IRLMX_EINVAL; }
@@ -2350,13 +2290,7 @@ static int validate(const irlmx_mdp* mdp) {
   return 0;
 }
 
-// Required array arguments of an entry point: NULL is rejected before any work
-// is enqueued (a null device pointer would fault the GPU).
-struct Arg {
-  const void* p;
-  const char* name;  // nullptr: optional argument
-};
-static int need_all(const char* fn, std::initializer_list<Arg> args) {
+int need_all(const char* fn, std::initializer_list<Arg> args) {
   for (const Arg& a : args)
     if (a.name && !a.p) {
       set_error("%s: %s is NULL", fn, a.name);
@@ -2519,14 +2453,36 @@ static bool bwd_compact(const Model& m, int* flag, hipStream_t st) {
 }
 }  // namespace irlmx
 
+// op carries IRLMX_PLAN_EXTENDED_RANGE (never true of a negative op, whose every
+// bit is set: those stay "unknown op")
+static bool extended_op(int op) { return op > 0 && (op & IRLMX_PLAN_EXTENDED_RANGE) != 0; }
+
+// The flag goes with IRLMX_OP_BACKWARD alone, on a model the extended pass runs.
+static int check_extended_op(const Model& m, int op, const char* fn) {
+  if (op != (IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE)) {
+    set_error("IRLMX_PLAN_EXTENDED_RANGE applies to IRLMX_OP_BACKWARD only (and not with IRLMX_PLAN_NO_RESCALE)");
+    return IRLMX_EINVAL;
+  }
+  return extended_check_model(m, fn);
+}
+
 extern "C" size_t irlmx_workspace_bytes(const irlmx_mdp* mdp, int32_t op) {
   if (validate(mdp)) return 0;
-  return carve(make_model(mdp), op, nullptr).total;
+  const Model m = make_model(mdp);
+  if (extended_op(op)) return check_extended_op(m, op, "workspace_bytes") ? 0 : extended_workspace_bytes(m);
+  return carve(m, op, nullptr).total;
 }
 
 extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* plan) {
   if (int rc = validate(mdp)) return rc;
   if (!plan) { set_error("plan is NULL"); return IRLMX_EINVAL; }
+  if (extended_op(op)) {
+    const Model m = make_model(mdp);
+    if (int rc = check_extended_op(m, op, "execution_plan")) return rc;
+    for (int i = 0; i < IRLMX_PLAN_LEN; ++i) plan[i] = 0;
+    extended_plan(m, plan);
+    return 0;
+  }
   // (a backward call with rescale = 0 never takes the cluster shape: see irlmx_backward_maxent)
   const bool no_rescale = op > 0 && (op & IRLMX_PLAN_NO_RESCALE) != 0;
   if (no_rescale) op &= ~IRLMX_PLAN_NO_RESCALE;

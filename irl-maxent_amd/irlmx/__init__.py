@@ -13,5 +13,6 @@ kernels for gfx950 behind the C ABI of ``libirlmx.so`` (include/irlmx.h).
 from ._lib import IrlmxError, load, require_device  # noqa: F401
 from .mdp import DeviceMDP  # noqa: F401
 from . import ops  # noqa: F401
+from .ops import backward_maxent_extended, execution_plan  # noqa: F401
 
 __version__ = "0.1.0"

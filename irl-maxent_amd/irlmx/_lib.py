@@ -25,6 +25,7 @@ SUCCESS = 0
 OK, NONFINITE, MAXITER = 0, 1, 2
 OP_BACKWARD, OP_FORWARD, OP_SOFT_BACKWARD, OP_VALUE_ITERATION = 1, 2, 3, 4
 PLAN_NO_RESCALE = 0x100
+PLAN_EXTENDED_RANGE = 0x200
 PROPS_KNOWN, PROP_COMPACT, PROP_ELL_SORTED = 0x40000000, 0x1, 0x2
 EINVAL, EHIP, EWORKSPACE = -1, -2, -3
 COUNTER_NAMES = ("cluster_launches", "grid_launches", "rerun_nonfinite", "rerun_not_resident", "rerun_timeout",
@@ -74,6 +75,7 @@ SIGNATURES = {
     "irlmx_device_checks_enabled": (ctypes.c_int, []),
     "irlmx_device_check_failures": (_I64, []),
     "irlmx_backward_maxent": (ctypes.c_int, [_MDP, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
+    "irlmx_backward_maxent_extended": (ctypes.c_int, [_MDP, _P, _P, _P, _P, _P, _SZ, _P]),
     "irlmx_backward_maxent_numpy_order": (ctypes.c_int, [_MDP, _P, _P, _P, _P, _P]),
     "irlmx_forward_svf_numpy_order": (ctypes.c_int, [_MDP, _P, _P, _P, _D, _I64, _P, _P, _P, _P]),
     "irlmx_forward_svf": (ctypes.c_int, [_MDP, _P, _P, _P, _D, _I64, _P, _P, _P, _P, _SZ, _P]),

@@ -37,7 +37,17 @@ split-K waves and the dense-grid row blocking from the working batch, each with
 its own per-row summation order (tested to 1e-9 against the uncompacted run).
 
 No host round trip happens inside a step except the forward pass's own
-convergence polling on the per-sweep shape.
+convergence polling on the per-sweep shape -- and, with
+``extended_range="auto"``, one device reduction and one host read per step
+(which instances hold a NaN or an exact 0 in their policy).
+
+Extended range (``extended_range``, non-causal only): the ordinary backward
+keeps one power-of-two scale per instance, so a partition vector that spans
+more than float64's exponent range (a reward contrast of 4 on a grid 256 wide)
+comes back with NaN rows and, beside them, finite rows that are wrong.
+``True`` runs every backward with one exponent per state
+(``ops.backward_maxent_extended``); ``"auto"`` reruns only the instances that
+show the symptom.
 """
 
 import numpy as np
@@ -63,11 +73,22 @@ def terminal_reward(terminal, n_states, batch=1, device=None):
 class BatchedMaxEnt:
     def __init__(self, mdp: DeviceMDP, e_features, p_initial, terminal, features=None, lr0=0.2,
                  eps_esvf=1e-5, theta0=1.0, rescale=True, causal=False, discount=None, eps_lap=1e-5,
-                 optimizer=None):
+                 optimizer=None, extended_range=False):
         """``theta0``: a float (the reference's Constant init, optimizer.py:369-398) or
         an array [F] or [B, F] (e.g. drawn with the reference's Uniform init,
         optimizer.py:334-366).  ``optimizer``: an irlmx.optim optimiser (default
-        ExpSga(linear_decay(lr0)), the reference main.py's choice)."""
+        ExpSga(linear_decay(lr0)), the reference main.py's choice).
+        ``extended_range`` (ignored with ``causal=True``: soft VI works in the log
+        domain already): ``False`` the ordinary backward; ``True`` every backward
+        runs ``ops.backward_maxent_extended``; ``"auto"`` after the ordinary
+        backward, the instances whose policy holds any NaN or any exact 0 are
+        recomputed with the extended pass and spliced in.  In a gridworld a zero
+        is either underflow or a state that cannot reach a terminal; in the
+        second case the rerun returns the same zero.  The check costs one device
+        reduction and one host read per step."""
+        if extended_range not in (False, True, "auto"):
+            raise ValueError(f"extended_range must be False, True or 'auto', got {extended_range!r}")
+        self.extended_range = extended_range
         self.mdp = mdp
         dev = mdp.device
         B, S = mdp.batch, mdp.n_states
@@ -189,7 +210,17 @@ class BatchedMaxEnt:
             pi, _, k, _ = ops.soft_backward(mdp, r, self._w("phi"), self.discount, self.eps_lap)
             self.last_backward_sweeps = self._scatter(k)
             return pi
-        return ops.backward_maxent(mdp, r, self._w("terminal"), rescale=self.rescale)
+        if self.extended_range is True:
+            return ops.backward_maxent_extended(mdp, r, self._w("terminal"))
+        pi = ops.backward_maxent(mdp, r, self._w("terminal"), rescale=self.rescale)
+        if self.extended_range == "auto":
+            suspect = (torch.isnan(pi) | (pi == 0)).flatten(1).any(dim=1)
+            idx = torch.nonzero(suspect).squeeze(1)          # (the host read: the index count)
+            if idx.numel():
+                sub = mdp.take(idx)
+                pi[idx] = ops.backward_maxent_extended(sub, r.index_select(0, idx),
+                                                       self._w("terminal").index_select(0, idx))
+        return pi
 
     def forward(self, pi):
         """``(svf [n, S], sweeps [n], status [n])`` of the working set (maxent.py:63-114)."""

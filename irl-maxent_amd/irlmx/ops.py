@@ -33,16 +33,21 @@ _OPS = {"backward": _lib.OP_BACKWARD, "forward": _lib.OP_FORWARD, "soft_backward
         "value_iteration": _lib.OP_VALUE_ITERATION}
 
 
-def execution_plan(mdp, op, rescale=True):
+def execution_plan(mdp, op, rescale=True, extended_range=False):
     """The kernel plan a call of ``op`` ("backward", "forward", "soft_backward",
     "value_iteration") on ``mdp`` runs on the current device (irlmx_execution_plan):
     shape, tile rows R, ghost rows G, tiles per instance C, instances per launch,
     states per lane, in-tile layout, threads, sequential launches, LDS bytes.
-    ``rescale=False``: the plan of ``backward_maxent(..., rescale=False)``."""
+    ``rescale=False``: the plan of ``backward_maxent(..., rescale=False)``.
+    ``extended_range=True`` (``op="backward"`` only): the plan of
+    ``backward_maxent_extended`` -- "fused", or "sweep" with its 2*S - 1 launches."""
     import ctypes
     lib = _lib.load()
     buf = (ctypes.c_int64 * len(PLAN_FIELDS))()
-    code = _OPS[op] | (0 if rescale or op != "backward" else _lib.PLAN_NO_RESCALE)
+    if extended_range:
+        code = _OPS[op] | _lib.PLAN_EXTENDED_RANGE
+    else:
+        code = _OPS[op] | (0 if rescale or op != "backward" else _lib.PLAN_NO_RESCALE)
     _lib.check(lib.irlmx_execution_plan(mdp.struct(), code, buf), "execution_plan")
     plan = dict(zip(PLAN_FIELDS, [int(v) for v in buf]))
     plan["shape"] = SHAPES[plan["shape"]]
@@ -99,6 +104,27 @@ def backward_maxent(mdp, reward, terminal, rescale=True):
     _lib.check(lib.irlmx_backward_maxent(mdp.struct(), _lib.ptr(r), _lib.ptr(term), 1 if rescale else 0,
                                          _lib.ptr(pi), _lib.ptr(status), _lib.ptr(ws), n,
                                          _lib.stream_ptr(mdp.device)), "backward_maxent")
+    return pi
+
+
+def backward_maxent_extended(mdp, reward, terminal):
+    """Local action probabilities [B, S, A] (maxent.py:119-159) with one exponent
+    per state (irlmx_backward_maxent_extended): finite, and right, where the
+    partition vector spans more than float64's exponent range and
+    ``backward_maxent`` returns NaN rows and wrong finite rows beside them;
+    bit-identical to ``backward_maxent`` where that pass stays in range.
+    STENCIL5 and ELL models.  Above 4096 states it runs one launch per sweep
+    (2*S - 1 launches: slow at config-4 size)."""
+    lib = _lib.load()
+    B, S, A = mdp.batch, mdp.n_states, mdp.n_actions
+    r = _f64(reward, mdp, (B, S))
+    term = terminal.to(device=mdp.device, dtype=torch.uint8).reshape(B, S).contiguous()
+    pi = torch.empty((B, S, A), dtype=torch.float64, device=mdp.device)
+    status = torch.empty(B, dtype=torch.int32, device=mdp.device)
+    ws, n = _workspace(mdp, _lib.OP_BACKWARD | _lib.PLAN_EXTENDED_RANGE)
+    _lib.check(lib.irlmx_backward_maxent_extended(mdp.struct(), _lib.ptr(r), _lib.ptr(term), _lib.ptr(pi),
+                                                  _lib.ptr(status), _lib.ptr(ws), n, _lib.stream_ptr(mdp.device)),
+               "backward_maxent_extended")
     return pi
 
 
@@ -312,5 +338,5 @@ def stochastic_policy(successor, weighted_value):
     return out
 
 
-__all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "forward_svf", "soft_backward",
+__all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "backward_maxent_extended", "forward_svf", "soft_backward",
            "value_iteration", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]

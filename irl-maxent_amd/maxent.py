@@ -25,6 +25,13 @@ Deliberate differences (documented in DESIGN.md):
   of two (ratio-exact), so the policy stays finite.
   ``IRLMX_REFERENCE_OVERFLOW=1`` keeps the reference's NaN instead.
 * ``p_transition`` may also be an ``irlmx.DeviceMDP`` already resident in HBM.
+* ``IRLMX_EXTENDED_RANGE=1``: wherever the backward would take the rescaled
+  tiled pass, it runs with one exponent per state instead
+  (``ops.backward_maxent_extended``), so the policy stays finite and right
+  where the partition vector spans more than float64's exponent range (the
+  rescaled pass keeps one scale per instance: NaN rows, and wrong finite rows
+  beside them).  The numpy-order attempt and ``IRLMX_REFERENCE_OVERFLOW=1``
+  keep precedence; unset, nothing changes.  DENSE tables are not covered.
 """
 
 import os
@@ -43,6 +50,10 @@ __all__ = ["feature_expectation_from_trajectories", "initial_probabilities_from_
 
 def _rescale():
     return os.environ.get("IRLMX_REFERENCE_OVERFLOW", "0") != "1"
+
+
+def _extended():
+    return os.environ.get("IRLMX_EXTENDED_RANGE", "0") == "1"
 
 
 def _model(p_transition):
@@ -131,6 +142,8 @@ def _backward(mdp, reward, term):
         pi = ops.backward_maxent_numpy_order(mdp, np.exp(reward), term)   # er = np.exp(reward), maxent.py:142
         if not _rescale() or bool(torch.isfinite(pi).all()):
             return pi
+    if _extended() and _rescale():
+        return ops.backward_maxent_extended(mdp, reward, term)
     return ops.backward_maxent(mdp, reward, term, rescale=_rescale())
 
 

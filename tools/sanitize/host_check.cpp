@@ -15,7 +15,11 @@
 //    C ABI's irlmx_execution_plan and irlmx_workspace_bytes, with invariants
 //    checked on every plan;
 //  * every argument-validation path of every entry point (null models, bad
-//    sizes, unknown layouts, NULL arrays, short workspaces), with the error text.
+//    sizes, unknown layouts, NULL arrays, short workspaces), with the error text;
+//  * the extended-range backward (extended.hip): its plan and workspace
+//    (IRLMX_PLAN_EXTENDED_RANGE) for every stencil and ELL model above, the
+//    flag's refusal on the other ops and on DENSE tables, and the validation
+//    and workspace paths of irlmx_backward_maxent_extended.
 //
 // Exit status 0 and "host_check ok" on success.
 
@@ -133,6 +137,51 @@ static void check_plan(const irlmx_mdp& m, int op, const int64_t* p, const char*
   }
 }
 
+static long long g_ext_shapes[3];
+
+// The extended-range backward's plan and workspace for one model
+// (IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE), and the flag on the other ops.
+static void extended_plan_and_workspace(const irlmx_mdp& m, const char* what) {
+  const int op = IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE;
+  int64_t p[IRLMX_PLAN_LEN];
+  for (auto& v : p) v = -7;
+  const int rc = irlmx_execution_plan(&m, op, p);
+  const size_t ws = irlmx_workspace_bytes(&m, op);
+  if (m.layout == IRLMX_LAYOUT_DENSE) {
+    CHECK(rc == IRLMX_EINVAL && strstr(irlmx_last_error(), "DENSE"), "%s: extended plan of a DENSE table rc %d", what, rc);
+    CHECK(ws == 0, "%s: extended workspace of a DENSE table %zu", what, ws);
+    return;
+  }
+  CHECK(rc == 0, "%s: extended plan rc %d (%s)", what, rc, irlmx_last_error());
+  if (rc) return;
+  const size_t S = (size_t)m.n_states, B = (size_t)m.batch;
+  const size_t K = m.layout == IRLMX_LAYOUT_STENCIL5 ? 5 : (size_t)m.k_row;
+  size_t floor = B * K * S * sizeof(double) + B * sizeof(int32_t);
+  CHECK(p[0] == IRLMX_SHAPE_FUSED || p[0] == IRLMX_SHAPE_SWEEP, "%s: extended shape %lld", what, (long long)p[0]);
+  CHECK(p[1] == 0 && p[2] == 0 && p[3] == 0 && p[4] == 0 && p[6] == 0, "%s: extended plan cluster fields", what);
+  if (p[0] == IRLMX_SHAPE_FUSED) {
+    ++g_ext_shapes[0];
+    CHECK(S <= 4096 && K <= 32, "%s: extended fused at S %zu K %zu", what, S, K);
+    CHECK(p[7] >= 64 && p[7] <= 1024 && p[7] % 64 == 0, "%s: extended fused threads %lld", what, (long long)p[7]);
+    CHECK(p[5] >= 1 && p[5] <= 4 && p[5] * p[7] >= (int64_t)S, "%s: extended fused spt %lld", what, (long long)p[5]);
+    CHECK(p[8] == 1 && p[9] == (int64_t)(24 * S) && p[9] <= 160 * 1024, "%s: extended fused LDS %lld", what,
+          (long long)p[9]);
+  } else {
+    ++g_ext_shapes[2];
+    CHECK(p[5] == 1 && p[7] == 256 && p[8] == 2 * (int64_t)S - 1 && p[9] == 0, "%s: extended sweep plan", what);
+    floor += B * S * 2 * (sizeof(double) + sizeof(int32_t));
+  }
+  CHECK(ws >= floor && ws <= floor + 8 * 256 && ws % 256 == 0, "%s: extended workspace %zu (floor %zu)", what, ws, floor);
+  for (int other = IRLMX_OP_FORWARD; other <= IRLMX_OP_VALUE_ITERATION; ++other) {
+    CHECK(irlmx_execution_plan(&m, other | IRLMX_PLAN_EXTENDED_RANGE, p) == IRLMX_EINVAL &&
+              strstr(irlmx_last_error(), "IRLMX_OP_BACKWARD only"),
+          "%s: extended flag on op %d", what, other);
+    CHECK(irlmx_workspace_bytes(&m, other | IRLMX_PLAN_EXTENDED_RANGE) == 0, "%s: extended workspace of op %d", what,
+          other);
+  }
+  CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_NO_RESCALE, p) == IRLMX_EINVAL, "%s: extended + no-rescale", what);
+}
+
 static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
   for (int op = IRLMX_OP_BACKWARD; op <= IRLMX_OP_VALUE_ITERATION; ++op) {
     char what[160];
@@ -147,6 +196,7 @@ static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
       int64_t p2[IRLMX_PLAN_LEN];
       CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_NO_RESCALE, p2) == 0, "%s: no-rescale plan", what);
       CHECK(p2[0] != IRLMX_SHAPE_CLUSTER, "%s: rescale=0 backward planned on the cluster shape", what);
+      extended_plan_and_workspace(m, what);
     }
     const size_t ws = irlmx_workspace_bytes(&m, op);
     const size_t floor = (op == IRLMX_OP_BACKWARD || op == IRLMX_OP_FORWARD)
@@ -160,6 +210,11 @@ static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
 static int run_bwd(const irlmx_mdp* m, void* reward, void* term, void* pi, void* status, void* ws, size_t n) {
   return irlmx_backward_maxent(m, (const double*)reward, (const uint8_t*)term, 1, (double*)pi, (int32_t*)status, ws,
                                n, nullptr);
+}
+
+static int run_ext(const irlmx_mdp* m, void* reward, void* term, void* pi, void* status, void* ws, size_t n) {
+  return irlmx_backward_maxent_extended(m, (const double*)reward, (const uint8_t*)term, (double*)pi, (int32_t*)status,
+                                        ws, n, nullptr);
 }
 
 static void expect(int rc, int want, const char* msg_part, const char* what) {
@@ -190,7 +245,13 @@ static void error_paths() {
   m = ell(25, 4, 3, 3, 1); m.row_idx = nullptr; bad.push_back({"ell row_idx", m, "ELL row form missing"});
   m = dense(25, 4, 1); m.col_val = nullptr; bad.push_back({"dense col_val", m, "missing"});
   m = dense(1 << 20, 4, 1); bad.push_back({"dense size", m, "too large"});
+  const int ext_op = IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE;
+  const size_t ext_need = irlmx_workspace_bytes(&good, ext_op);
+  CHECK(ext_need > 0, "extended workspace of a good model");
+  expect(run_ext(nullptr, f, f, f, f, f, ext_need), IRLMX_EINVAL, "mdp is NULL", "extended null mdp");
   for (const Bad& b : bad) {
+    expect(run_ext(&b.m, f, f, f, f, f, ext_need), IRLMX_EINVAL, b.msg, b.name);
+    CHECK(irlmx_workspace_bytes(&b.m, ext_op) == 0, "%s: extended workspace of an invalid model", b.name);
     expect(run_bwd(&b.m, f, f, f, f, f, need), IRLMX_EINVAL, b.msg, b.name);
     int64_t plan[IRLMX_PLAN_LEN];
     expect(irlmx_execution_plan(&b.m, IRLMX_OP_FORWARD, plan), IRLMX_EINVAL, b.msg, b.name);
@@ -202,6 +263,26 @@ static void error_paths() {
   expect(run_bwd(&good, f, f, f, nullptr, f, need), IRLMX_EINVAL, "status is NULL", "null status");
   expect(run_bwd(&good, f, f, f, f, f, need - 1), IRLMX_EWORKSPACE, "workspace too small", "short workspace");
   expect(run_bwd(&good, f, f, f, f, nullptr, need), IRLMX_EWORKSPACE, "workspace too small", "null workspace");
+  expect(run_ext(&good, nullptr, f, f, f, f, ext_need), IRLMX_EINVAL, "backward_maxent_extended: reward is NULL",
+         "extended null reward");
+  expect(run_ext(&good, f, nullptr, f, f, f, ext_need), IRLMX_EINVAL, "terminal is NULL", "extended null terminal");
+  expect(run_ext(&good, f, f, nullptr, f, f, ext_need), IRLMX_EINVAL, "p_action is NULL", "extended null p_action");
+  expect(run_ext(&good, f, f, f, nullptr, f, ext_need), IRLMX_EINVAL, "status is NULL", "extended null status");
+  expect(run_ext(&good, f, f, f, f, f, ext_need - 1), IRLMX_EWORKSPACE, "workspace too small", "extended short workspace");
+  expect(run_ext(&good, f, f, f, f, f, 0), IRLMX_EWORKSPACE, "workspace too small", "extended empty workspace");
+  expect(run_ext(&good, f, f, f, f, nullptr, ext_need), IRLMX_EWORKSPACE, "workspace too small",
+         "extended null workspace");
+  {
+    irlmx_mdp d = dense(25, 4, 1);
+    expect(run_ext(&d, f, f, f, f, f, ext_need), IRLMX_EINVAL, "DENSE", "extended dense");
+    irlmx_mdp big = stencil((1 << 19) + 1, 1, 4, 1, 1);
+    expect(run_ext(&big, f, f, f, f, f, ext_need), IRLMX_EINVAL, "at most 524288 states", "extended S > 2^19");
+    int64_t p[IRLMX_PLAN_LEN];
+    expect(irlmx_execution_plan(&big, ext_op, p), IRLMX_EINVAL, "at most 524288 states", "extended plan S > 2^19");
+    irlmx_mdp wide = ell(100, 4, 40, 3, 2);  // more slots than any fused kernel holds: per sweep
+    expect(irlmx_execution_plan(&wide, ext_op, p), IRLMX_OK, "", "extended plan K = 40");
+    CHECK(p[0] == IRLMX_SHAPE_SWEEP, "extended plan K = 40: shape %lld", (long long)p[0]);
+  }
   expect(irlmx_forward_svf(&good, (double*)f, (uint8_t*)f, (double*)f, 1e-5, 0, (double*)f, nullptr, (int32_t*)f, f,
                            1 << 30, nullptr),
          IRLMX_EINVAL, "iterations is NULL", "forward null iterations");
@@ -294,6 +375,12 @@ int main() {
             g_shapes[IRLMX_SHAPE_DENSE_GRID] > 0,
         "every shape planned: fused %lld cluster %lld sweep %lld dense %lld gemm %lld grid %lld dense-grid %lld",
         g_shapes[0], g_shapes[1], g_shapes[2], g_shapes[3], g_shapes[4], g_shapes[5], g_shapes[6]);
+  if (g_fail) {
+    fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
+    return 1;
+  }
+  CHECK(g_ext_shapes[0] > 100 && g_ext_shapes[2] > 100, "extended shapes planned: fused %lld sweep %lld",
+        g_ext_shapes[0], g_ext_shapes[2]);
   if (g_fail) {
     fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
     return 1;
