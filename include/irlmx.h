@@ -57,6 +57,7 @@ extern "C" {
 #define IRLMX_OP_FORWARD 2
 #define IRLMX_OP_SOFT_BACKWARD 3
 #define IRLMX_OP_VALUE_ITERATION 4
+#define IRLMX_OP_POLICY_EVALUATION 6 /* 5 stays an unknown op: ABI version 1 has always answered "unknown op 5" */
 
 /*
  * Transition model P[from, to, action] of B instances (the reference's dense
@@ -267,6 +268,40 @@ int irlmx_value_iteration(const irlmx_mdp* mdp, const double* reward, double dis
                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Policy evaluation -- the value of a given stochastic policy (no reference
+ * counterpart: solver.stochastic_value_iteration, src/solver.py:55-104, is the
+ * uniform policy only): v <- r + gamma * sum_a pi_a * (P_a v) from v = 0
+ * (solver.py:32) until max|v' - v| <= eps.  With it the expected value
+ * difference p0 . (v* - v^pi) of a recovered reward is computed on the device.
+ *   reward   [B][S]     the reward the policy is judged under
+ *   p_action [B][S][A]  pi[s, a]; rows need not be normalised (weights, not
+ *            probabilities, to the kernels): a MaxEnt policy with an exact-0 row
+ *            is legal input and gives v(s) = r(s)
+ *   terminal [B][S] or NULL: a state whose byte is set gets all-zero weights, so
+ *            its successors contribute nothing and v(s) = r(s) bit for bit (the
+ *            cleared terminal rows of maxent.py:98-99); NULL: no terminal
+ *            handling, like solver.value_iteration
+ *   value [B][S] out; iterations [B] out (int64); status [B] out
+ * Statement order, the same in every shape (bit-identical values, sweep counts
+ * and status):
+ *   once per call  w[k][s] = sum_a pi[s, a] * P[s, target_k(s), a]: A fused
+ *                  multiply-adds in action order from 0 (0 at terminal states)
+ *   per sweep      acc = fma(w[k][s], v[target_k(s)], acc) in slot order from 0,
+ *                  v'(s) = r(s) + gamma * acc: the product rounded, then the sum
+ * The loop stops after the first sweep with max|v' - v| <= eps (IRLMX_OK), on a
+ * NaN delta (IRLMX_NONFINITE) or at max_iter > 0 sweeps (IRLMX_MAXITER).
+ * STENCIL5 and ELL layouts; IRLMX_EINVAL for DENSE and for a discount outside
+ * [0, 1] (NaN included).  Models of at most 4096 states (ELL: at most 32 slots)
+ * run one workgroup per instance, fully asynchronous; larger ones one launch
+ * per sweep with a host poll -- there is no persistent multi-CU form of this
+ * pass.  Workspace: irlmx_workspace_bytes(mdp, IRLMX_OP_POLICY_EVALUATION).
+ */
+int irlmx_policy_evaluation(const irlmx_mdp* mdp, const double* reward, const double* p_action,
+                            const uint8_t* terminal /* may be NULL */, double discount, double eps,
+                            int64_t max_iter, double* value, int64_t* iterations, int32_t* status,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Soft value iteration and value iteration in numpy's own floating-point order
  * (no reference counterpart beyond maxent.py:326-341 / solver.py:40-50, 95-100
  * themselves): every p[a].dot(v) / p[a] @ v summed as numpy's OpenBLAS dgemv_t
@@ -301,6 +336,9 @@ int irlmx_value_iteration_numpy_order(const irlmx_mdp* mdp, const double* reward
  *       backward plan checks the table on the device and synchronises)
  *   [7] threads per workgroup  [8] sequential launches   [9] LDS bytes
  * Cluster fields are 0 for the other shapes.  Depends on the current device.
+ * IRLMX_OP_POLICY_EVALUATION plans the fused shape ([5], [7], [8] = 1, [9]) or
+ * the per-sweep one ([5] = 1, [7]; [8] = 0: its launch count is the sweep
+ * count); IRLMX_EINVAL for DENSE, here and 0 from irlmx_workspace_bytes.
  * A backward plan assumes rescale != 0 unless op carries IRLMX_PLAN_NO_RESCALE.
  */
 #define IRLMX_PLAN_LEN 10

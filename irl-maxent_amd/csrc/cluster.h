@@ -244,11 +244,6 @@ __device__ inline unsigned scale_code(double m) {
 __device__ inline int code_exponent(unsigned c) {
   return (c == 0u || c == kCodeNonFinite) ? 0 : -((int)c - (int)kCodeBias);
 }
-__device__ inline unsigned long long wave_or_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off, kWave);
-  return v;
-}
 
 // cluster_run's result when a forward instance turned non-finite: the call must
 // be rerun on the per-sweep shape (exact NaN bookkeeping; cluster.hip)

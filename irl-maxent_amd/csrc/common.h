@@ -83,6 +83,12 @@ __device__ inline unsigned long long wave_max_u64(unsigned long long v) {
   return v;
 }
 
+__device__ inline unsigned long long wave_or_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off, kWave);
+  return v;
+}
+
 // np.maximum / np.minimum: NaN-propagating elementwise max/min.
 __device__ inline double np_maximum(double a, double b) {
   return (a != a || b != b) ? (a + b) : (a > b ? a : b);

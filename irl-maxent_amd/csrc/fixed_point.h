@@ -1,6 +1,7 @@
-// Model views and host helpers of the fixed-point passes that more than one
-// translation unit uses (fixed_point.hip defines the host functions;
-// extended.hip is the other user).
+// Model views, the workspace, the stopping-rule helpers and the host helpers of
+// the fixed-point passes that more than one translation unit uses
+// (fixed_point.hip defines the host functions; extended.hip and
+// policy_eval.hip are the other users).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -76,6 +77,183 @@ __device__ inline int col_src(const Model& m, int b, int t, int k) {
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // ---------------------------------------------------------------------------
+// workspace (carve(), fixed_point.hip)
+// ---------------------------------------------------------------------------
+
+struct Ws {
+  double* wgt;                // forward: [B][Kc][S] gather weights; backward: [B][K][S] reward-folded;
+                              // policy evaluation: [B][K][S] policy-folded
+  int32_t* bad;               // [B] forward: policy has a non-finite entry
+  double* buf0;               // [B][S]   sweep path ping
+  double* buf1;               // [B][S]   sweep path pong
+  unsigned long long* slots;  // [B][3]
+  int32_t* done;              // [B]
+  int64_t* iters;             // [B]
+  int32_t* ndone;             // [1]
+  // cluster shape (stencil layouts too large for one CU); sizes as carve() takes them:
+  unsigned long long* gran;   // cluster: [B][gran_inst_len(W, H)] x 16 B (two padded halo parities, cluster.h);
+                              // grid: [B][3][S] x 16 B; dense grid: [B][2][S] x 16 B
+  unsigned long long* sgran;  // cluster: [B][kSumRows][H] x 16 B (tile summaries by block % kSumSlots,
+                              // then the XCC ids and the forward's full flags, cluster.h); grid: [B][4][bpi]; dense grid: [B][bpi] x 16 B
+  unsigned long long* growth; // [2][B] growth / decay bounds (bwd_growth_kernel)
+  int* err;                   // [4]: error bits, rendezvous counters
+  size_t total;
+};
+
+// The workspace of `op` (IRLMX_OP_*) on this model, carved from `base` (nullptr: sizes only).
+Ws carve(const Model& m, int op, void* base);
+// IRLMX_EWORKSPACE and the message unless `bytes` at `ws` hold carve(m, op).total.
+int check_ws(const Model& m, int op, size_t bytes, void* ws);
+
+// ---------------------------------------------------------------------------
+// the stopping rule, fused shape
+// ---------------------------------------------------------------------------
+
+__device__ inline int finish_status(double delta, double eps) {
+  if (delta != delta) return IRLMX_NONFINITE;
+  return delta > eps ? IRLMX_MAXITER : IRLMX_OK;
+}
+
+// The reference's fixed-point loops stop after the first sweep whose
+// max|x_new - x| is not > eps, NaN included (maxent.py:108, :335, solver.py:49).
+// run_deferred keeps that rule without a per-sweep reduction: each lane records
+// per sweep i "some |x_new - x| > eps" (bit i) and "some |x_new - x| is NaN"
+// (bit 32 + i) for its states (record_delta), and the workgroup ORs the bits
+// once per block of kDeferBlock sweeps.  If the block holds the stopping sweep
+// k, restore() puts the block-start state back (LDS and registers; save() took
+// it) and sweeps 0..k are replayed -- the same arithmetic, so the same bits.
+// sweep(it, pos, bits) runs one sweep from buffer parity it & 1 and records at
+// bit pos (the helpers put the barrier after it); slot[0..2] are zero on entry.
+// Returns the status (OK, NONFINITE, MAXITER); `it` counts the sweeps done.
+// One call site of sweep(), so it is inlined once.  run_each is the per-sweep
+// form for kernels whose registers have no room for the block bookkeeping: the
+// same bits, reduced every sweep with two ballots (no cross-lane shuffles).
+constexpr int kDeferBlock = 32;
+__device__ inline void record_delta(unsigned long long& bits, int pos, double d, double eps) {
+  bits |= ((d > eps) ? 1ull : 0ull) << pos;
+  bits |= ((d != d) ? 1ull : 0ull) << (32 + pos);
+}
+template <class Sweep, class Save, class Restore>
+__device__ __attribute__((always_inline)) inline int run_deferred(long long max_iter, unsigned long long* slot,
+                                                                  long long& it, Sweep&& sweep, Save&& save,
+                                                                  Restore&& restore) {
+  const int tid = threadIdx.x;
+  for (int blk = 0;; ++blk) {
+    save();
+    int nb = kDeferBlock;
+    if (max_iter > 0) nb = (int)min<long long>(nb, max_iter - it);
+    int k = -1;
+    unsigned nan = 0u;
+    for (int pass = 0; pass < 2; ++pass) {  // the block, then (stop inside it) the replay
+      unsigned long long bits = 0ull;
+      const int cnt = pass == 0 ? nb : k + 1;
+      for (int i = 0; i < cnt; ++i) {
+        sweep(it + i, i, bits);
+        __syncthreads();
+      }
+      if (pass == 1) break;
+      bits = wave_or_u64(bits);
+      if ((tid & (kWave - 1)) == 0 && bits) atomicOr(&slot[blk & 1], bits);
+      if (tid == 0) slot[(blk & 1) ^ 1] = 0ull;  // last read in the previous block, before this block's barriers
+      __syncthreads();
+      const unsigned long long all = slot[blk & 1];
+      const unsigned gt = (unsigned)all;
+      nan = (unsigned)(all >> 32);
+      const unsigned live = nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u);
+      const unsigned stop = (~gt | nan) & live;
+      if (!stop) break;
+      k = __builtin_ctz(stop);
+      restore();
+    }
+    if (k >= 0) {
+      it += k + 1;
+      return ((nan >> k) & 1u) ? IRLMX_NONFINITE : IRLMX_OK;
+    }
+    it += nb;
+    if (max_iter > 0 && it >= max_iter) return IRLMX_MAXITER;
+  }
+}
+template <class Sweep>
+__device__ __attribute__((always_inline)) inline int run_each(long long max_iter, unsigned long long* slot,
+                                                              long long& it, Sweep&& sweep) {
+  const int tid = threadIdx.x;
+  for (int r3 = 0;; r3 = r3 == 2 ? 0 : r3 + 1) {
+    unsigned long long bits = 0ull;
+    sweep(it, 0, bits);
+    const unsigned long long w = (__builtin_amdgcn_ballot_w64((bits & 1ull) != 0ull) ? 1ull : 0ull) |
+                                 (__builtin_amdgcn_ballot_w64((bits >> 32) != 0ull) ? (1ull << 32) : 0ull);
+    if ((tid & (kWave - 1)) == 0 && w) atomicOr(&slot[r3], w);
+    if (tid == 0) slot[r3 == 2 ? 0 : r3 + 1] = 0ull;  // read two sweeps ago
+    __syncthreads();
+    const unsigned long long all = slot[r3];
+    ++it;
+    if (all >> 32) return IRLMX_NONFINITE;
+    if (!(all & 1ull)) return IRLMX_OK;
+    if (max_iter > 0 && it >= max_iter) return IRLMX_MAXITER;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// the stopping rule, per-sweep shape
+// ---------------------------------------------------------------------------
+
+__device__ inline void block_max_to(unsigned long long v, unsigned long long* dst) {
+  __shared__ unsigned long long red[kSweepThreads / kWave];
+  v = wave_max_u64(v);
+  const int wv = threadIdx.x / kWave;
+  if ((threadIdx.x & (kWave - 1)) == 0) red[wv] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long m = 0;
+    for (int i = 0; i < (int)(blockDim.x / kWave); ++i) m = red[i] > m ? red[i] : m;
+    if (m) atomicMax(dst, m);
+  }
+}
+
+// Common prologue: decides whether instance b converged after the previous
+// sweep (`it` sweeps done so far); the first workgroup records the outcome.
+__device__ inline bool sweep_should_stop(int b, long long it, int r3, double eps, long long max_iter,
+                                         const Ws& ws, int32_t* status) {
+  if (ws.done[b]) return true;
+  if (it == 0) return false;
+  const double prev = bits_double(ws.slots[b * 3 + (r3 == 0 ? 2 : r3 - 1)]);
+  const bool cap = max_iter > 0 && it >= max_iter;
+  if (prev > eps && !cap) return false;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ws.done[b] = 1;
+    ws.iters[b] = it;
+    status[b] = finish_status(prev, eps);
+    atomicAdd(ws.ndone, 1);
+  }
+  return true;
+}
+
+// Host poll loop of the sweep shape: enqueue `chunk` sweeps, read the done
+// counter, repeat.  Converged instances skip their sweeps, so over-enqueueing
+// costs only empty launches.
+template <typename LaunchOne>
+static int run_until_done(const Ws& ws, int B, hipStream_t st, LaunchOne&& one) {
+  long long it = 0;
+  int r3 = 0;
+  long long chunk = 32;
+  for (;;) {
+    for (long long c = 0; c < chunk; ++c) {
+      one(it, r3);
+      ++it;
+      r3 = r3 == 2 ? 0 : r3 + 1;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "sweep launch");
+    int32_t nd = 0;
+    e = hipMemcpyAsync(&nd, ws.ndone, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "poll");
+    if (nd >= B) return 0;
+    if (chunk < 4096) chunk *= 2;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host helpers (fixed_point.hip)
 // ---------------------------------------------------------------------------
 
@@ -100,6 +278,28 @@ struct FusedShape {
   int threads;
 };
 bool fused_shape(const Model& m, int op, FusedShape* out, bool cluster_first = true);
+// (SPT, KMAX) pairs instantiated per op -- the one list fused_shape plans from
+// and every kernel-pointer getter instantiates from: every pair listed compiles
+// without VGPR spills at __launch_bounds__(1024) (tools/kernel_resources.py);
+// the soft pass carries fp64 exp/log inline and so keeps fewer states per thread.
+constexpr bool fused_pair_ok(int op, int spt, int kmax) {
+  switch (op) {
+    case IRLMX_OP_FORWARD:
+    case IRLMX_OP_BACKWARD:
+    case IRLMX_OP_POLICY_EVALUATION:  // (policy_eval.hip: the backward's register layout)
+      return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt <= 2) ||
+             (kmax == 32 && spt == 1);
+    case IRLMX_OP_SOFT_BACKWARD:
+      return (kmax == 5 && spt <= 2) || (kmax == 8 && spt == 1) || (kmax == 16 && spt == 1);
+    case IRLMX_OP_VALUE_ITERATION:
+      return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 4) || (kmax == 16 && spt == 1) ||
+             (kmax == 32 && spt == 1);
+  }
+  return false;
+}
+// LDS of the ordinary fused kernels: two S-vectors, the convergence slots and
+// run_deferred's block-start snapshot.
+size_t fused_lds(const Model& m);
 
 // Enqueue bwd_weights_kernel: w[b][k][s] = exp(r[b][s]) * sum_a P[s, target_k(s), a],
 // bad[b] |= 1 where a weight is non-finite (bwd_nonfinite_rule).
@@ -112,5 +312,9 @@ void bwd_weights_launch(const Model& m, const double* reward, double* w, int32_t
 int extended_check_model(const Model& m, const char* fn);
 size_t extended_workspace_bytes(const Model& m);
 void extended_plan(const Model& m, int64_t* plan);
+
+// Policy evaluation (policy_eval.hip): whether this model is one it runs (else
+// IRLMX_EINVAL and the message, prefixed by `fn`).
+int policy_eval_check_model(const Model& m, const char* fn);
 
 }  // namespace irlmx

@@ -55,25 +55,6 @@ int fused_max_states() {
 // workspace carving
 // ---------------------------------------------------------------------------
 
-struct Ws {
-  double* wgt;                // forward: [B][Kc][S] gather weights; backward: [B][K][S] reward-folded
-  int32_t* bad;               // [B] forward: policy has a non-finite entry
-  double* buf0;               // [B][S]   sweep path ping
-  double* buf1;               // [B][S]   sweep path pong
-  unsigned long long* slots;  // [B][3]
-  int32_t* done;              // [B]
-  int64_t* iters;             // [B]
-  int32_t* ndone;             // [1]
-  // cluster shape (stencil layouts too large for one CU); sizes as carve() takes them:
-  unsigned long long* gran;   // cluster: [B][gran_inst_len(W, H)] x 16 B (two padded halo parities, cluster.h);
-                              // grid: [B][3][S] x 16 B; dense grid: [B][2][S] x 16 B
-  unsigned long long* sgran;  // cluster: [B][kSumRows][H] x 16 B (tile summaries by block % kSumSlots,
-                              // then the XCC ids and the forward's full flags, cluster.h); grid: [B][4][bpi]; dense grid: [B][bpi] x 16 B
-  unsigned long long* growth; // [2][B] growth / decay bounds (bwd_growth_kernel)
-  int* err;                   // [4]: error bits, rendezvous counters
-  size_t total;
-};
-
 static bool use_fused(const Model& m, int op);
 
 // Persistent grid shape (soft VI / VI on stencil grids too large for one CU):
@@ -85,7 +66,7 @@ static bool grid_plan(const Model& m, int op, GridPlan* out);
 // Persistent dense shape (dense_grid.hip) for this call, if it applies.
 static bool dense_grid(const Model& m, int op, DenseGridPlan* out);
 
-static Ws carve(const Model& m, int op, void* base) {
+Ws carve(const Model& m, int op, void* base) {
   Ws w;
   size_t off = 0;
   char* p = (char*)base;
@@ -98,6 +79,7 @@ static Ws carve(const Model& m, int op, void* base) {
   size_t nw = 0;
   if (op == IRLMX_OP_FORWARD) nw = B * m.Kc * S;  // dense: the per-instance gather matrices WT [B][S][S]
   if (op == IRLMX_OP_BACKWARD) nw = m.dense ? B * S : B * m.K * S;  // reward-folded; dense: the GEMM product
+  if (op == IRLMX_OP_POLICY_EVALUATION) nw = B * m.K * S;           // policy-folded (policy_eval.hip)
   if ((op == IRLMX_OP_SOFT_BACKWARD || op == IRLMX_OP_VALUE_ITERATION) && m.dense && m.shared)
     nw = (size_t)m.A * B * S;  // the per-action GEMM products of a shared dense table
   w.wgt = (double*)take(nw * sizeof(double));
@@ -233,90 +215,6 @@ struct FwdArgs {
   int64_t* iters;
   int32_t* status;
 };
-
-__device__ inline int finish_status(double delta, double eps) {
-  if (delta != delta) return IRLMX_NONFINITE;
-  return delta > eps ? IRLMX_MAXITER : IRLMX_OK;
-}
-
-// The reference's fixed-point loops stop after the first sweep whose
-// max|x_new - x| is not > eps, NaN included (maxent.py:108, :335, solver.py:49).
-// run_deferred keeps that rule without a per-sweep reduction: each lane records
-// per sweep i "some |x_new - x| > eps" (bit i) and "some |x_new - x| is NaN"
-// (bit 32 + i) for its states (record_delta), and the workgroup ORs the bits
-// once per block of kDeferBlock sweeps.  If the block holds the stopping sweep
-// k, restore() puts the block-start state back (LDS and registers; save() took
-// it) and sweeps 0..k are replayed -- the same arithmetic, so the same bits.
-// sweep(it, pos, bits) runs one sweep from buffer parity it & 1 and records at
-// bit pos (the helpers put the barrier after it); slot[0..2] are zero on entry.
-// Returns the status (OK, NONFINITE, MAXITER); `it` counts the sweeps done.
-// One call site of sweep(), so it is inlined once.  run_each is the per-sweep
-// form for kernels whose registers have no room for the block bookkeeping: the
-// same bits, reduced every sweep with two ballots (no cross-lane shuffles).
-constexpr int kDeferBlock = 32;
-__device__ inline void record_delta(unsigned long long& bits, int pos, double d, double eps) {
-  bits |= ((d > eps) ? 1ull : 0ull) << pos;
-  bits |= ((d != d) ? 1ull : 0ull) << (32 + pos);
-}
-template <class Sweep, class Save, class Restore>
-__device__ __attribute__((always_inline)) inline int run_deferred(long long max_iter, unsigned long long* slot,
-                                                                  long long& it, Sweep&& sweep, Save&& save,
-                                                                  Restore&& restore) {
-  const int tid = threadIdx.x;
-  for (int blk = 0;; ++blk) {
-    save();
-    int nb = kDeferBlock;
-    if (max_iter > 0) nb = (int)min<long long>(nb, max_iter - it);
-    int k = -1;
-    unsigned nan = 0u;
-    for (int pass = 0; pass < 2; ++pass) {  // the block, then (stop inside it) the replay
-      unsigned long long bits = 0ull;
-      const int cnt = pass == 0 ? nb : k + 1;
-      for (int i = 0; i < cnt; ++i) {
-        sweep(it + i, i, bits);
-        __syncthreads();
-      }
-      if (pass == 1) break;
-      bits = wave_or_u64(bits);
-      if ((tid & (kWave - 1)) == 0 && bits) atomicOr(&slot[blk & 1], bits);
-      if (tid == 0) slot[(blk & 1) ^ 1] = 0ull;  // last read in the previous block, before this block's barriers
-      __syncthreads();
-      const unsigned long long all = slot[blk & 1];
-      const unsigned gt = (unsigned)all;
-      nan = (unsigned)(all >> 32);
-      const unsigned live = nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u);
-      const unsigned stop = (~gt | nan) & live;
-      if (!stop) break;
-      k = __builtin_ctz(stop);
-      restore();
-    }
-    if (k >= 0) {
-      it += k + 1;
-      return ((nan >> k) & 1u) ? IRLMX_NONFINITE : IRLMX_OK;
-    }
-    it += nb;
-    if (max_iter > 0 && it >= max_iter) return IRLMX_MAXITER;
-  }
-}
-template <class Sweep>
-__device__ __attribute__((always_inline)) inline int run_each(long long max_iter, unsigned long long* slot,
-                                                              long long& it, Sweep&& sweep) {
-  const int tid = threadIdx.x;
-  for (int r3 = 0;; r3 = r3 == 2 ? 0 : r3 + 1) {
-    unsigned long long bits = 0ull;
-    sweep(it, 0, bits);
-    const unsigned long long w = (__builtin_amdgcn_ballot_w64((bits & 1ull) != 0ull) ? 1ull : 0ull) |
-                                 (__builtin_amdgcn_ballot_w64((bits >> 32) != 0ull) ? (1ull << 32) : 0ull);
-    if ((tid & (kWave - 1)) == 0 && w) atomicOr(&slot[r3], w);
-    if (tid == 0) slot[r3 == 2 ? 0 : r3 + 1] = 0ull;  // read two sweeps ago
-    __syncthreads();
-    const unsigned long long all = slot[r3];
-    ++it;
-    if (all >> 32) return IRLMX_NONFINITE;
-    if (!(all & 1ull)) return IRLMX_OK;
-    if (max_iter > 0 && it >= max_iter) return IRLMX_MAXITER;
-  }
-}
 
 // one barrier per sweep; LDS: two S-vectors + 3 convergence slots
 template <int SPT, int KMAX>
@@ -1435,37 +1333,6 @@ __global__ void __launch_bounds__(1024) vi_fused_kernel(SoftArgs a) {
 // sweep (one launch per sweep, all instances) kernels
 // ---------------------------------------------------------------------------
 
-__device__ inline void block_max_to(unsigned long long v, unsigned long long* dst) {
-  __shared__ unsigned long long red[kSweepThreads / kWave];
-  v = wave_max_u64(v);
-  const int wv = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) red[wv] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long m = 0;
-    for (int i = 0; i < (int)(blockDim.x / kWave); ++i) m = red[i] > m ? red[i] : m;
-    if (m) atomicMax(dst, m);
-  }
-}
-
-// Common prologue: decides whether instance b converged after the previous
-// sweep (`it` sweeps done so far); the first workgroup records the outcome.
-__device__ inline bool sweep_should_stop(int b, long long it, int r3, double eps, long long max_iter,
-                                         const Ws& ws, int32_t* status) {
-  if (ws.done[b]) return true;
-  if (it == 0) return false;
-  const double prev = bits_double(ws.slots[b * 3 + (r3 == 0 ? 2 : r3 - 1)]);
-  const bool cap = max_iter > 0 && it >= max_iter;
-  if (prev > eps && !cap) return false;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    ws.done[b] = 1;
-    ws.iters[b] = it;
-    status[b] = finish_status(prev, eps);
-    atomicAdd(ws.ndone, 1);
-  }
-  return true;
-}
-
 __global__ void __launch_bounds__(kSweepThreads)
 fwd_sweep_kernel(FwdArgs a, Ws ws, long long it, int r3) {
   const Model& m = a.m;
@@ -2183,24 +2050,6 @@ static int pick_kmax(int K) {
   return 0;
 }
 
-// (SPT, KMAX) pairs instantiated per op: every pair listed compiles without
-// VGPR spills at __launch_bounds__(1024) (tools/kernel_resources.py); the soft
-// pass carries fp64 exp/log inline and so keeps fewer states per thread.
-static constexpr bool fused_pair_ok(int op, int spt, int kmax) {
-  switch (op) {
-    case IRLMX_OP_FORWARD:
-    case IRLMX_OP_BACKWARD:
-      return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt <= 2) ||
-             (kmax == 32 && spt == 1);
-    case IRLMX_OP_SOFT_BACKWARD:
-      return (kmax == 5 && spt <= 2) || (kmax == 8 && spt == 1) || (kmax == 16 && spt == 1);
-    case IRLMX_OP_VALUE_ITERATION:
-      return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 4) || (kmax == 16 && spt == 1) ||
-             (kmax == 32 && spt == 1);
-  }
-  return false;
-}
-
 bool fused_shape(const Model& m, int op, FusedShape* out, bool cluster_first) {
   if (m.dense || m.S > fused_max_states() || m.A > kMaxActions) return false;
   // Grids of width 64 / 128 run the forward and backward passes on the cluster
@@ -2229,7 +2078,7 @@ static bool use_fused(const Model& m, int op) {
 }
 
 // two S-vectors, the convergence slots and (run_deferred) the block-start snapshot
-static size_t fused_lds(const Model& m) { return 3 * (size_t)m.S * sizeof(double) + 4 * sizeof(unsigned long long); }
+size_t fused_lds(const Model& m) { return 3 * (size_t)m.S * sizeof(double) + 4 * sizeof(unsigned long long); }
 
 // Kernel-pointer getters: only the (SPT, KMAX) pairs fused_pair_ok() admits
 // are instantiated.
@@ -2299,38 +2148,13 @@ int need_all(const char* fn, std::initializer_list<Arg> args) {
   return 0;
 }
 
-static int check_ws(const Model& m, int op, size_t bytes, void* ws) {
+int check_ws(const Model& m, int op, size_t bytes, void* ws) {
   const size_t need = carve(m, op, nullptr).total;
   if (bytes < need || (need && !ws)) {
     set_error("workspace too small: need %zu bytes, got %zu", need, bytes);
     return IRLMX_EWORKSPACE;
   }
   return 0;
-}
-
-// Host poll loop of the sweep shape: enqueue `chunk` sweeps, read the done
-// counter, repeat.  Converged instances skip their sweeps, so over-enqueueing
-// costs only empty launches.
-template <typename LaunchOne>
-static int run_until_done(const Ws& ws, int B, hipStream_t st, LaunchOne&& one) {
-  long long it = 0;
-  int r3 = 0;
-  long long chunk = 32;
-  for (;;) {
-    for (long long c = 0; c < chunk; ++c) {
-      one(it, r3);
-      ++it;
-      r3 = r3 == 2 ? 0 : r3 + 1;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "sweep launch");
-    int32_t nd = 0;
-    e = hipMemcpyAsync(&nd, ws.ndone, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e, "poll");
-    if (nd >= B) return 0;
-    if (chunk < 4096) chunk *= 2;
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2470,6 +2294,7 @@ extern "C" size_t irlmx_workspace_bytes(const irlmx_mdp* mdp, int32_t op) {
   if (validate(mdp)) return 0;
   const Model m = make_model(mdp);
   if (extended_op(op)) return check_extended_op(m, op, "workspace_bytes") ? 0 : extended_workspace_bytes(m);
+  if (op == IRLMX_OP_POLICY_EVALUATION && policy_eval_check_model(m, "workspace_bytes")) return 0;
   return carve(m, op, nullptr).total;
 }
 
@@ -2486,9 +2311,15 @@ extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* p
   // (a backward call with rescale = 0 never takes the cluster shape: see irlmx_backward_maxent)
   const bool no_rescale = op > 0 && (op & IRLMX_PLAN_NO_RESCALE) != 0;
   if (no_rescale) op &= ~IRLMX_PLAN_NO_RESCALE;
-  if (op < IRLMX_OP_BACKWARD || op > IRLMX_OP_VALUE_ITERATION) { set_error("unknown op %d", op); return IRLMX_EINVAL; }
+  // (IRLMX_OP_POLICY_EVALUATION is 6: the value between stays the unknown op it has always been)
+  if (op < IRLMX_OP_BACKWARD || (op > IRLMX_OP_VALUE_ITERATION && op != IRLMX_OP_POLICY_EVALUATION)) {
+    set_error("unknown op %d", op);
+    return IRLMX_EINVAL;
+  }
   if (no_rescale && op != IRLMX_OP_BACKWARD) { set_error("IRLMX_PLAN_NO_RESCALE applies to IRLMX_OP_BACKWARD only"); return IRLMX_EINVAL; }
   const Model m = make_model(mdp);
+  if (op == IRLMX_OP_POLICY_EVALUATION)
+    if (int rc = policy_eval_check_model(m, "execution_plan")) return rc;
   for (int i = 0; i < IRLMX_PLAN_LEN; ++i) plan[i] = 0;
   FusedShape fs;
   if (fused_shape(m, op, &fs)) {
@@ -2552,6 +2383,7 @@ extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* p
   }
   plan[0] = IRLMX_SHAPE_SWEEP;
   plan[7] = kSweepThreads;
+  if (op == IRLMX_OP_POLICY_EVALUATION) plan[5] = 1;  // one state per lane; the launch count is the sweep count
   return 0;
 }
 

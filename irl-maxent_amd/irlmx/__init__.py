@@ -4,7 +4,8 @@ Host side in Python on PyTorch-ROCm tensors, compute in hand-written HIP
 kernels for gfx950 behind the C ABI of ``libirlmx.so`` (include/irlmx.h).
 
 * ``irlmx.DeviceMDP``  -- transition model resident in HBM (stencil / ELL)
-* ``irlmx.ops``        -- batched device ops: backward, forward SVF, soft VI, VI
+* ``irlmx.ops``        -- batched device ops: backward, forward SVF, soft VI, VI,
+  policy evaluation and the expected value difference
 * ``irlmx.batch``      -- batched IRL gradient steps (B instances per call)
 * ``maxent`` / ``solver`` (next to this package) -- numpy drop-ins for the
   reference modules of the same names.
@@ -14,5 +15,6 @@ from ._lib import IrlmxError, load, require_device  # noqa: F401
 from .mdp import DeviceMDP  # noqa: F401
 from . import ops  # noqa: F401
 from .ops import backward_maxent_extended, execution_plan  # noqa: F401
+from .ops import expected_value_difference, policy_evaluation  # noqa: F401
 
 __version__ = "0.1.0"

@@ -252,6 +252,26 @@ class BatchedMaxEnt:
         self.update(svf)
         return svf
 
+    def expected_value_difference(self, true_reward, discount, eps=1e-3):
+        """Expected value difference ``p0 . (v* - v_pi)`` of the current theta under
+        ``true_reward`` ([S] or [B, S]), per instance: a [B] tensor in original
+        instance order, also after compaction.  pi is the current theta's
+        backward policy on all B instances (stopped ones included: their theta
+        is their result); p0 and the terminals are this object's own
+        (ops.expected_value_difference).  Reads theta only: theta, the step
+        counter, the active set and the compaction state stay as they are."""
+        work, sweeps = self._work, self.last_backward_sweeps
+        self._work = None          # the full batch, in original order
+        try:
+            pi = self.backward()
+        finally:
+            self._work, self.last_backward_sweeps = work, sweeps
+        B, S = self.batch, self.mdp.n_states
+        r = torch.as_tensor(true_reward, dtype=torch.float64, device=self.theta.device)
+        r = r.expand(B, S) if r.dim() == 1 else r.reshape(B, S)
+        return ops.expected_value_difference(self.mdp, r.contiguous(), pi, self.p_initial, discount, self.terminal,
+                                             eps)[0]
+
     def prime_compaction(self, eps=1e-4):
         """Run, once, every device operation of ``run()`` outside the passes --
         the stop test, ``compact()`` and ``update()`` on a working set, the

@@ -30,12 +30,14 @@ def _workspace(mdp, op):
 PLAN_FIELDS = ("shape", "R", "G", "C", "per_launch", "spt", "layout", "threads", "launches", "lds_bytes")
 SHAPES = {0: "fused", 1: "cluster", 2: "sweep", 3: "dense", 4: "dense-gemm", 5: "grid", 6: "dense-grid"}
 _OPS = {"backward": _lib.OP_BACKWARD, "forward": _lib.OP_FORWARD, "soft_backward": _lib.OP_SOFT_BACKWARD,
-        "value_iteration": _lib.OP_VALUE_ITERATION}
+        "value_iteration": _lib.OP_VALUE_ITERATION, "policy_evaluation": _lib.OP_POLICY_EVALUATION}
+_OPS.update({code: code for code in list(_OPS.values())})   # the _lib.OP_* codes themselves are accepted too
 
 
 def execution_plan(mdp, op, rescale=True, extended_range=False):
     """The kernel plan a call of ``op`` ("backward", "forward", "soft_backward",
-    "value_iteration") on ``mdp`` runs on the current device (irlmx_execution_plan):
+    "value_iteration", "policy_evaluation", or its ``_lib.OP_*`` code) on ``mdp``
+    runs on the current device (irlmx_execution_plan):
     shape, tile rows R, ghost rows G, tiles per instance C, instances per launch,
     states per lane, in-tile layout, threads, sequential launches, LDS bytes.
     ``rescale=False``: the plan of ``backward_maxent(..., rescale=False)``.
@@ -47,7 +49,7 @@ def execution_plan(mdp, op, rescale=True, extended_range=False):
     if extended_range:
         code = _OPS[op] | _lib.PLAN_EXTENDED_RANGE
     else:
-        code = _OPS[op] | (0 if rescale or op != "backward" else _lib.PLAN_NO_RESCALE)
+        code = _OPS[op] | (0 if rescale or _OPS[op] != _lib.OP_BACKWARD else _lib.PLAN_NO_RESCALE)
     _lib.check(lib.irlmx_execution_plan(mdp.struct(), code, buf), "execution_plan")
     plan = dict(zip(PLAN_FIELDS, [int(v) for v in buf]))
     plan["shape"] = SHAPES[plan["shape"]]
@@ -286,6 +288,81 @@ def value_iteration(mdp, reward, discount, eps=1e-3, average=False, max_iter=0, 
     return v, iters, status
 
 
+def policy_evaluation(mdp, reward, p_action, discount, terminal=None, eps=1e-3, max_iter=0):
+    """Value of the stochastic policy ``p_action`` [B, S, A] under ``reward``
+    (irlmx_policy_evaluation): ``v <- r + discount * sum_a pi_a * (P_a v)`` from
+    ``v = 0`` until ``max|dv| <= eps``.
+
+    Returns ``(value [B, S], iterations [B], status [B])``.  ``terminal`` (a
+    uint8 [B, S] mask, see :func:`terminal_mask`): those states get
+    ``v(s) = r(s)``, their successors contribute nothing (the cleared rows of
+    maxent.py:98-99); ``None``: no terminal handling, like ``value_iteration``.
+    The rows of ``p_action`` need not be normalised: a MaxEnt policy with an
+    exact-0 row is legal and gives ``v(s) = r(s)``.  STENCIL5 and ELL models.
+    """
+    lib = _lib.load()
+    B, S, A = mdp.batch, mdp.n_states, mdp.n_actions
+    r = _f64(reward, mdp, (B, S))
+    pi = _f64(p_action, mdp, (B, S, A))
+    term = None if terminal is None else terminal.to(device=mdp.device, dtype=torch.uint8).reshape(B, S).contiguous()
+    v = torch.empty((B, S), dtype=torch.float64, device=mdp.device)
+    iters = torch.empty(B, dtype=torch.int64, device=mdp.device)
+    status = torch.empty(B, dtype=torch.int32, device=mdp.device)
+    ws, n = _workspace(mdp, _lib.OP_POLICY_EVALUATION)
+    _lib.check(lib.irlmx_policy_evaluation(mdp.struct(), _lib.ptr(r), _lib.ptr(pi), _lib.ptr(term), float(discount),
+                                           float(eps), int(max_iter), _lib.ptr(v), _lib.ptr(iters), _lib.ptr(status),
+                                           _lib.ptr(ws), n, _lib.stream_ptr(mdp.device)), "policy_evaluation")
+    return v, iters, status
+
+
+def _row_targets(mdp):
+    """Target state of every stored slot, int64 [tables, K, S] on the device."""
+    if mdp.layout == _lib.LAYOUT_ELL:
+        return mdp.row_idx.to(torch.int64).clamp(0, mdp.n_states - 1)   # (a slot of value 0 may hold any index)
+    if mdp.layout != _lib.LAYOUT_STENCIL5:
+        raise ValueError("STENCIL5 and ELL models only")
+    W, H = mdp.width, mdp.height
+    s = torch.arange(mdp.n_states, dtype=torch.int64, device=mdp.device)
+    x, y = s % W, s // W
+    nb = torch.stack([s, torch.where(x + 1 < W, s + 1, s), torch.where(x > 0, s - 1, s),
+                      torch.where(y + 1 < H, s + W, s), torch.where(y > 0, s - W, s)])
+    return nb.unsqueeze(0)
+
+
+def _greedy_one_hot(mdp, value):
+    """One-hot [B, S, A] of ``argmax_a (P_a value)(s)``, first index on ties: the
+    policy hard-max value iteration's last sweep follows.  One pass of torch
+    tensor operations over the stored slots (not a fixed-point loop)."""
+    B, S, A = mdp.batch, mdp.n_states, mdp.n_actions
+    nb = _row_targets(mdp)                                           # [T, K, S]
+    vn = value.unsqueeze(1).expand(B, nb.shape[1], S).gather(2, nb.expand(B, -1, -1))   # [B, K, S]
+    q = (mdp.row_val.to(torch.float64) * vn.unsqueeze(1)).sum(dim=2)          # [B, A, S]
+    return torch.nn.functional.one_hot(q.argmax(dim=1), A).to(torch.float64)  # [B, S, A]
+
+
+def expected_value_difference(mdp, true_reward, p_action, p_initial, discount, terminal=None, eps=1e-3):
+    """Expected value difference of a policy under the *true* reward:
+    ``evd[b] = sum_s p0[b, s] * (v*[b, s] - v_pi[b, s])``, on the device.
+
+    Returns ``(evd [B], v_opt [B, S], v_pi [B, S])``.  ``v_pi`` is
+    :func:`policy_evaluation` of ``p_action``.  Without ``terminal``, ``v*`` is
+    ``value_iteration(mdp, true_reward, discount, eps)``.  ``value_iteration``
+    has no terminal argument, so with ``terminal`` ``v*`` is the evaluation
+    (same ``terminal``, same ``eps``) of the greedy one-hot policy of that value
+    iteration: the optimal policy's value in the model whose terminal states
+    end the episode.  Both values are truncated fixed points (each within
+    ``eps * discount / (1 - discount)`` of its limit), so the difference of an
+    optimal policy can be slightly negative.
+    """
+    B, S = mdp.batch, mdp.n_states
+    v_opt, _, _ = value_iteration(mdp, true_reward, discount, eps)
+    if terminal is not None:
+        v_opt, _, _ = policy_evaluation(mdp, true_reward, _greedy_one_hot(mdp, v_opt), discount, terminal, eps)
+    v_pi, _, _ = policy_evaluation(mdp, true_reward, p_action, discount, terminal, eps)
+    p0 = _f64(p_initial, mdp, (B, S))
+    return (p0 * (v_opt - v_pi)).sum(dim=1), v_opt, v_pi
+
+
 def dense_gemm(m, z):
     """``z @ m.T`` on the fp64 matrix cores (irlmx_dense_gemm): m [R, S], z [B, S]
     float64 device tensors -> [B, R].  The batched P . [v_1 .. v_B] contraction
@@ -339,4 +416,4 @@ def stochastic_policy(successor, weighted_value):
 
 
 __all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "backward_maxent_extended", "forward_svf", "soft_backward",
-           "value_iteration", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]
+           "value_iteration", "policy_evaluation", "expected_value_difference", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]

@@ -15,7 +15,7 @@ import torch
 from irlmx import DeviceMDP, ops
 
 __all__ = ["value_iteration", "stochastic_value_iteration", "optimal_policy_from_value",
-           "optimal_policy", "stochastic_policy_from_value"]
+           "optimal_policy", "stochastic_policy_from_value", "policy_evaluation", "expected_value_difference"]
 
 
 def _model(p):
@@ -41,6 +41,50 @@ def stochastic_value_iteration(p, reward, discount, eps=1e-3):
     mdp = _model(p)
     v, _, _ = ops.value_iteration(mdp, reward, discount, eps, average=True, numpy_order=_np_order(mdp))
     return v[0].cpu().numpy()
+
+
+def _policy_table(policy, n_states, n_actions):
+    """``policy`` as an (S, A) float64 table: action probabilities as they are,
+    an (S,) integer array (optimal_policy's result) expanded to one-hot."""
+    policy = np.asarray(policy)
+    if policy.ndim == 1 and np.issubdtype(policy.dtype, np.integer):
+        if policy.shape != (n_states,) or policy.min() < 0 or policy.max() >= n_actions:
+            raise ValueError(f"integer policy must hold {n_states} actions in [0, {n_actions})")
+        table = np.zeros((n_states, n_actions))
+        table[np.arange(n_states), policy] = 1.0
+        return table
+    if policy.shape != (n_states, n_actions):
+        raise ValueError(f"policy must have shape ({n_states}, {n_actions}) or be ({n_states},) integers, "
+                         f"got {policy.shape} {policy.dtype}")
+    return policy.astype(np.float64)
+
+
+def _terminal_mask(mdp, terminal):
+    return None if terminal is None else ops.terminal_mask(terminal, mdp.n_states, device=mdp.device)
+
+
+def policy_evaluation(p, reward, policy, discount, eps=1e-3, terminal=None):
+    """Value of ``policy`` under ``reward``: v <- r + discount * sum_a pi_a * (P_a v)
+    from 0 until max|dv| <= eps (no reference counterpart: the reference
+    evaluates the uniform policy only, solver.py:55-104).  ``policy``: (S, A)
+    action probabilities, or the (S,) integer array optimal_policy returns.
+    ``terminal``: states whose value is their reward (their successors
+    contribute nothing).  Returns an (S,) float64 array."""
+    mdp = _model(p)
+    pi = _policy_table(policy, mdp.n_states, mdp.n_actions)
+    v, _, _ = ops.policy_evaluation(mdp, reward, pi, discount, _terminal_mask(mdp, terminal), eps)
+    return v[0].cpu().numpy()
+
+
+def expected_value_difference(p, true_reward, policy, p_initial, discount, eps=1e-3, terminal=None):
+    """p_initial . (v* - v_policy) under ``true_reward``, a float: how much value
+    the policy (of a recovered reward) loses against the optimal one
+    (ops.expected_value_difference, which also says what v* is with terminals)."""
+    mdp = _model(p)
+    pi = _policy_table(policy, mdp.n_states, mdp.n_actions)
+    evd, _, _ = ops.expected_value_difference(mdp, true_reward, pi, p_initial, discount,
+                                              _terminal_mask(mdp, terminal), eps)
+    return float(evd[0])
 
 
 def _uses_grid_transition(world):

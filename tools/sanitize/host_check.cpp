@@ -19,7 +19,13 @@
 //  * the extended-range backward (extended.hip): its plan and workspace
 //    (IRLMX_PLAN_EXTENDED_RANGE) for every stencil and ELL model above, the
 //    flag's refusal on the other ops and on DENSE tables, and the validation
-//    and workspace paths of irlmx_backward_maxent_extended.
+//    and workspace paths of irlmx_backward_maxent_extended;
+//  * policy evaluation (policy_eval.hip): the plan and workspace of
+//    IRLMX_OP_POLICY_EVALUATION for every stencil and ELL model above (fused or
+//    per sweep, never a persistent shape), its refusal of DENSE tables and of
+//    the backward-only flags, and every validation path of
+//    irlmx_policy_evaluation (NULL arrays, discount outside [0, 1] or NaN,
+//    short workspace).
 //
 // Exit status 0 and "host_check ok" on success.
 
@@ -182,6 +188,51 @@ static void extended_plan_and_workspace(const irlmx_mdp& m, const char* what) {
   CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_NO_RESCALE, p) == IRLMX_EINVAL, "%s: extended + no-rescale", what);
 }
 
+static long long g_pe_shapes[3];
+
+// Policy evaluation's plan and workspace for one model (IRLMX_OP_POLICY_EVALUATION):
+// fused or per sweep, never a persistent shape; refused on DENSE tables.
+static void policy_eval_plan_and_workspace(const irlmx_mdp& m, const char* what) {
+  const int op = IRLMX_OP_POLICY_EVALUATION;
+  int64_t p[IRLMX_PLAN_LEN];
+  for (auto& v : p) v = -7;
+  const int rc = irlmx_execution_plan(&m, op, p);
+  const size_t ws = irlmx_workspace_bytes(&m, op);
+  if (m.layout == IRLMX_LAYOUT_DENSE) {
+    CHECK(rc == IRLMX_EINVAL && strstr(irlmx_last_error(), "DENSE"), "%s: policy evaluation plan of a DENSE table rc %d",
+          what, rc);
+    CHECK(ws == 0, "%s: policy evaluation workspace of a DENSE table %zu", what, ws);
+    return;
+  }
+  CHECK(rc == 0, "%s: policy evaluation plan rc %d (%s)", what, rc, irlmx_last_error());
+  if (rc) return;
+  const size_t S = (size_t)m.n_states, B = (size_t)m.batch;
+  const size_t K = m.layout == IRLMX_LAYOUT_STENCIL5 ? 5 : (size_t)m.k_row;
+  size_t floor = B * K * S * sizeof(double) + B * (3 * sizeof(uint64_t) + sizeof(int32_t) + sizeof(int64_t));
+  CHECK(p[0] == IRLMX_SHAPE_FUSED || p[0] == IRLMX_SHAPE_SWEEP, "%s: policy evaluation shape %lld", what, (long long)p[0]);
+  CHECK(p[1] == 0 && p[2] == 0 && p[3] == 0 && p[4] == 0 && p[6] == 0, "%s: policy evaluation plan cluster fields", what);
+  if (p[0] == IRLMX_SHAPE_FUSED) {
+    ++g_pe_shapes[0];
+    CHECK(S <= 4096 && K <= 32, "%s: policy evaluation fused at S %zu K %zu", what, S, K);
+    CHECK(p[7] >= 64 && p[7] <= 1024 && p[7] % 64 == 0, "%s: policy evaluation fused threads %lld", what, (long long)p[7]);
+    CHECK(p[5] >= 1 && p[5] <= 4 && p[5] * p[7] >= (int64_t)S, "%s: policy evaluation fused spt %lld", what, (long long)p[5]);
+    CHECK(p[8] == 1 && p[9] == (int64_t)(24 * S + 32) && p[9] <= 160 * 1024, "%s: policy evaluation fused LDS %lld", what,
+          (long long)p[9]);
+  } else {
+    ++g_pe_shapes[2];
+    CHECK(p[5] == 1 && p[7] == 256 && p[8] == 0 && p[9] == 0, "%s: policy evaluation sweep plan", what);
+    floor += B * S * 2 * sizeof(double);
+  }
+  CHECK(ws >= floor && ws <= floor + 16 * 256 && ws % 256 == 0, "%s: policy evaluation workspace %zu (floor %zu)", what, ws,
+        floor);
+  CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_EXTENDED_RANGE, p) == IRLMX_EINVAL &&
+            strstr(irlmx_last_error(), "IRLMX_OP_BACKWARD only"),
+        "%s: extended flag on policy evaluation", what);
+  CHECK(irlmx_workspace_bytes(&m, op | IRLMX_PLAN_EXTENDED_RANGE) == 0, "%s: extended workspace of policy evaluation", what);
+  CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_NO_RESCALE, p) == IRLMX_EINVAL && strstr(irlmx_last_error(), "NO_RESCALE"),
+        "%s: no-rescale flag on policy evaluation", what);
+}
+
 static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
   for (int op = IRLMX_OP_BACKWARD; op <= IRLMX_OP_VALUE_ITERATION; ++op) {
     char what[160];
@@ -197,6 +248,7 @@ static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
       CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_NO_RESCALE, p2) == 0, "%s: no-rescale plan", what);
       CHECK(p2[0] != IRLMX_SHAPE_CLUSTER, "%s: rescale=0 backward planned on the cluster shape", what);
       extended_plan_and_workspace(m, what);
+      policy_eval_plan_and_workspace(m, what);
     }
     const size_t ws = irlmx_workspace_bytes(&m, op);
     const size_t floor = (op == IRLMX_OP_BACKWARD || op == IRLMX_OP_FORWARD)
@@ -215,6 +267,12 @@ static int run_bwd(const irlmx_mdp* m, void* reward, void* term, void* pi, void*
 static int run_ext(const irlmx_mdp* m, void* reward, void* term, void* pi, void* status, void* ws, size_t n) {
   return irlmx_backward_maxent_extended(m, (const double*)reward, (const uint8_t*)term, (double*)pi, (int32_t*)status,
                                         ws, n, nullptr);
+}
+
+static int run_pe(const irlmx_mdp* m, void* reward, void* pi, void* term, double discount, void* value, void* iters,
+                  void* status, void* ws, size_t n) {
+  return irlmx_policy_evaluation(m, (const double*)reward, (const double*)pi, (const uint8_t*)term, discount, 1e-3, 0,
+                                 (double*)value, (int64_t*)iters, (int32_t*)status, ws, n, nullptr);
 }
 
 static void expect(int rc, int want, const char* msg_part, const char* what) {
@@ -282,6 +340,41 @@ static void error_paths() {
     irlmx_mdp wide = ell(100, 4, 40, 3, 2);  // more slots than any fused kernel holds: per sweep
     expect(irlmx_execution_plan(&wide, ext_op, p), IRLMX_OK, "", "extended plan K = 40");
     CHECK(p[0] == IRLMX_SHAPE_SWEEP, "extended plan K = 40: shape %lld", (long long)p[0]);
+  }
+  {  // irlmx_policy_evaluation: every validation path, in the order the entry checks them
+    const size_t pe_need = irlmx_workspace_bytes(&good, IRLMX_OP_POLICY_EVALUATION);
+    CHECK(pe_need > 0, "policy evaluation workspace of a good model");
+    expect(run_pe(nullptr, f, f, f, 0.9, f, f, f, f, pe_need), IRLMX_EINVAL, "mdp is NULL", "policy evaluation null mdp");
+    for (const Bad& b : bad) {
+      expect(run_pe(&b.m, f, f, f, 0.9, f, f, f, f, pe_need), IRLMX_EINVAL, b.msg, b.name);
+      CHECK(irlmx_workspace_bytes(&b.m, IRLMX_OP_POLICY_EVALUATION) == 0, "%s: policy evaluation workspace of an invalid model",
+            b.name);
+    }
+    irlmx_mdp d = dense(25, 4, 1);
+    expect(run_pe(&d, f, f, f, 0.9, f, f, f, f, pe_need), IRLMX_EINVAL, "DENSE", "policy evaluation dense");
+    expect(run_pe(&good, nullptr, f, f, 0.9, f, f, f, f, pe_need), IRLMX_EINVAL, "policy_evaluation: reward is NULL",
+           "policy evaluation null reward");
+    expect(run_pe(&good, f, nullptr, f, 0.9, f, f, f, f, pe_need), IRLMX_EINVAL, "p_action is NULL",
+           "policy evaluation null p_action");
+    expect(run_pe(&good, f, f, f, 0.9, nullptr, f, f, f, pe_need), IRLMX_EINVAL, "value is NULL", "policy evaluation null value");
+    expect(run_pe(&good, f, f, f, 0.9, f, nullptr, f, f, pe_need), IRLMX_EINVAL, "iterations is NULL",
+           "policy evaluation null iterations");
+    expect(run_pe(&good, f, f, f, 0.9, f, f, nullptr, f, pe_need), IRLMX_EINVAL, "status is NULL",
+           "policy evaluation null status");
+    expect(run_pe(&good, f, f, f, 1.5, f, f, f, f, pe_need), IRLMX_EINVAL, "outside [0, 1]", "policy evaluation discount 1.5");
+    expect(run_pe(&good, f, f, f, -0.5, f, f, f, f, pe_need), IRLMX_EINVAL, "outside [0, 1]", "policy evaluation discount < 0");
+    expect(run_pe(&good, f, f, f, strtod("nan", nullptr), f, f, f, f, pe_need), IRLMX_EINVAL, "outside [0, 1]",
+           "policy evaluation discount NaN");
+    expect(run_pe(&good, f, f, nullptr, 0.9, f, f, f, f, pe_need - 1), IRLMX_EWORKSPACE, "workspace too small",
+           "policy evaluation short workspace (terminal NULL is legal)");
+    expect(run_pe(&good, f, f, f, 0.9, f, f, f, nullptr, pe_need), IRLMX_EWORKSPACE, "workspace too small",
+           "policy evaluation null workspace");
+    int64_t p[IRLMX_PLAN_LEN];
+    irlmx_mdp wide = ell(100, 4, 40, 3, 2);  // more slots than any fused kernel holds: per sweep
+    expect(irlmx_execution_plan(&wide, IRLMX_OP_POLICY_EVALUATION, p), IRLMX_OK, "", "policy evaluation plan K = 40");
+    CHECK(p[0] == IRLMX_SHAPE_SWEEP, "policy evaluation plan K = 40: shape %lld", (long long)p[0]);
+    expect(irlmx_execution_plan(&good, IRLMX_OP_POLICY_EVALUATION + 1, p), IRLMX_EINVAL, "unknown op 7", "op 7");
+    expect(irlmx_execution_plan(&good, 5, p), IRLMX_EINVAL, "unknown op 5", "op 5 (never an op)");
   }
   expect(irlmx_forward_svf(&good, (double*)f, (uint8_t*)f, (double*)f, 1e-5, 0, (double*)f, nullptr, (int32_t*)f, f,
                            1 << 30, nullptr),
@@ -381,6 +474,12 @@ int main() {
   }
   CHECK(g_ext_shapes[0] > 100 && g_ext_shapes[2] > 100, "extended shapes planned: fused %lld sweep %lld",
         g_ext_shapes[0], g_ext_shapes[2]);
+  if (g_fail) {
+    fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
+    return 1;
+  }
+  CHECK(g_pe_shapes[0] > 100 && g_pe_shapes[2] > 100, "policy evaluation shapes planned: fused %lld sweep %lld",
+        g_pe_shapes[0], g_pe_shapes[2]);
   if (g_fail) {
     fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
     return 1;
