@@ -302,6 +302,82 @@ int irlmx_policy_evaluation(const irlmx_mdp* mdp, const double* reward, const do
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Demonstrations on the device (no reference counterpart beyond the statistics
+ * of maxent.py:15-60: the reference samples with numpy's global generator,
+ * trajectory.py:52-128, which the trajectory.py drop-in follows draw for draw).
+ * One thread per trajectory; all three calls are fully asynchronous on
+ * `stream` and need no workspace.  STENCIL5 and ELL layouts; IRLMX_EINVAL for
+ * DENSE.  Per-trajectory outcome codes (written to traj_status):
+ */
+#define IRLMX_TRAJ_OK 0         /* reached a terminal state */
+#define IRLMX_TRAJ_TRUNCATED 1  /* still alive after max_len steps */
+#define IRLMX_TRAJ_BAD_POLICY 2 /* a policy row with no positive finite total, or a negative or NaN entry */
+#define IRLMX_TRAJ_BAD_TABLE 3  /* the same for the transition row of the drawn action, or the drawn ELL
+                                   target outside [0, S) */
+#define IRLMX_TRAJ_BAD_INDEX 4  /* a start state outside [0, S); in the two calls on stored trajectories a
+                                   stored state or action out of range or a length outside [0, stride - 1] */
+/*
+ * The index checks behind codes 3 and 4 run in every build (not only with
+ * IRLMX_DEVICE_CHECKS): a bad index ends its trajectory with the code and is
+ * never used as an index.
+ *
+ * irlmx_rollout samples n_traj trajectories per instance from explicit start
+ * states under the policy p_action:
+ *   p_action [B][S][A]  weights of the actions per state (rows need not be
+ *            normalised: a MaxEnt policy is not, exactly)
+ *   terminal [B][S]     a trajectory ends when it enters a state whose byte is set
+ *   start    [B][N]     start state of each trajectory
+ *   seed     [B]        one 64-bit seed per instance
+ *   max_len  1 .. 2^20  step cap per trajectory: the upper limit keeps a kernel
+ *            from running unboundedly on a shared GPU (a policy that never
+ *            reaches a terminal is legal input); IRLMX_EINVAL outside
+ *   visits [B][S] out   visits of each state, the final state of every
+ *            trajectory included (maxent.py:15-39 with identity features, times
+ *            n_traj); starts [B][S] out: trajectories starting in each state
+ *            (maxent.py:42-60, times n_traj).  Both zeroed by the call itself.
+ *   lengths [B][N] out  steps taken; traj_status [B][N] out
+ *   states [B][N][max_len + 1], actions [B][N][max_len]  out, both NULL or
+ *            both set: states 0..length and actions 0..length - 1 of each
+ *            trajectory; entries beyond are not written (nothing at all for a
+ *            bad start state)
+ * Random numbers: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl
+ * constants 0x9E3779B9, 0xBB67AE85), one block per step with counter
+ * (t, n, 0, 0) -- step t of trajectory n -- and key (low, high word of
+ * seed[b]).  The stream of a trajectory therefore depends on its instance's
+ * seed, n and t only: not on B, the instance's place in the batch or the launch.
+ * From the output words x0..x3, u_action = ((x1 >> 5) * 2^26 + (x0 >> 6)) * 2^-53
+ * and u_next likewise from x3, x2.  Both draws use one rule, pick(u, w): total =
+ * the sum of w in index order; the row is invalid (codes 2 / 3) if an entry is
+ * negative or NaN or total is not positive and finite; the result is the first
+ * j with u * total < w_0 + .. + w_j, or the last j with w_j > 0 when the product
+ * rounded up to total.  A slot of weight 0 is never drawn.  Per step in a
+ * non-terminal state s: count s, a = pick(u_action, p_action[b][s][:]),
+ * k = pick(u_next, P[s, target_k(s), a] over the K slots), s' = target_k(s).
+ * However a trajectory stops, its current state is counted once more as its
+ * final state; a terminal start state gives length 0.  Integer counts and a
+ * counter-based generator: the results are the same bits on every run.
+ *
+ * irlmx_demo_statistics recomputes visits and starts (zeroed by the call) from
+ * stored trajectories: states [B][N][stride] (entries 0..length read), lengths
+ * [B][N].  A trajectory with code 4 counts nothing.
+ *
+ * irlmx_demo_log_likelihood: ll_traj[b][n] = sum over t < length of
+ * log p_action[b][s_t][a_t], numpy's log (irlmx_numpy_math), added in step order;
+ * log 0 = -inf is a legal result.  actions [B][N][stride - 1].  ll[b] = the sum of
+ * ll_traj[b][:] in index order; a trajectory with code 4 has ll_traj = NaN.
+ */
+int irlmx_rollout(const irlmx_mdp* mdp, const double* p_action, const uint8_t* terminal, const int32_t* start,
+                  const uint64_t* seed, int32_t n_traj, int32_t max_len, int64_t* visits, int64_t* starts,
+                  int32_t* lengths, int32_t* traj_status, int32_t* states /* may be NULL */,
+                  int32_t* actions /* may be NULL */, void* stream);
+int irlmx_demo_statistics(int32_t n_states, int32_t batch, int32_t n_traj, int32_t stride /* states row length */,
+                          const int32_t* states, const int32_t* lengths, int64_t* visits, int64_t* starts,
+                          int32_t* traj_status, void* stream);
+int irlmx_demo_log_likelihood(int32_t n_states, int32_t n_actions, int32_t batch, int32_t n_traj, int32_t stride,
+                              const double* p_action, const int32_t* states, const int32_t* actions,
+                              const int32_t* lengths, double* ll_traj, double* ll, int32_t* traj_status, void* stream);
+
+/*
  * Soft value iteration and value iteration in numpy's own floating-point order
  * (no reference counterpart beyond maxent.py:326-341 / solver.py:40-50, 95-100
  * themselves): every p[a].dot(v) / p[a] @ v summed as numpy's OpenBLAS dgemv_t

@@ -29,6 +29,9 @@ PLAN_NO_RESCALE = 0x100
 PLAN_EXTENDED_RANGE = 0x200
 PROPS_KNOWN, PROP_COMPACT, PROP_ELL_SORTED = 0x40000000, 0x1, 0x2
 EINVAL, EHIP, EWORKSPACE = -1, -2, -3
+TRAJ_OK, TRAJ_TRUNCATED, TRAJ_BAD_POLICY, TRAJ_BAD_TABLE, TRAJ_BAD_INDEX = 0, 1, 2, 3, 4   # IRLMX_TRAJ_*
+TRAJ_NAMES = ("ok", "truncated", "bad policy row", "bad table row", "bad index")
+ROLLOUT_MAX_LEN = 1 << 20
 COUNTER_NAMES = ("cluster_launches", "grid_launches", "rerun_nonfinite", "rerun_not_resident", "rerun_timeout",
                  "sweep_calls")   # IRLMX_CTR_* order
 
@@ -85,6 +88,9 @@ SIGNATURES = {
     "irlmx_value_iteration_numpy_order": (ctypes.c_int, [_MDP, _P, _D, _D, _I32, _I64, _P, _P, _P, _P]),
     "irlmx_value_iteration": (ctypes.c_int, [_MDP, _P, _D, _D, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
     "irlmx_policy_evaluation": (ctypes.c_int, [_MDP, _P, _P, _P, _D, _D, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "irlmx_rollout": (ctypes.c_int, [_MDP, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "irlmx_demo_statistics": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "irlmx_demo_log_likelihood": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "irlmx_execution_plan": (ctypes.c_int, [_MDP, _I32, _P]),
     "irlmx_optimal_policy": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
     "irlmx_stochastic_policy": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),

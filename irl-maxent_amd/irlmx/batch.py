@@ -272,6 +272,45 @@ class BatchedMaxEnt:
         return ops.expected_value_difference(self.mdp, r.contiguous(), pi, self.p_initial, discount, self.terminal,
                                              eps)[0]
 
+    def log_likelihood(self, states, actions, lengths):
+        """Mean per-trajectory log-likelihood of stored demonstrations (``states``
+        [B, N, L + 1], ``actions`` [B, N, L], ``lengths`` [B, N], as
+        ``ops.rollout`` returns them) under the current theta's backward policy,
+        per instance: a [B] tensor in original instance order, also after
+        compaction (``ops.demo_log_likelihood``'s sum over N).  The score that
+        needs no true reward; -inf where a demonstration takes an action the
+        policy gives probability 0.  Reads theta only: theta, the step counter,
+        the active set and the compaction state stay as they are."""
+        work, sweeps = self._work, self.last_backward_sweeps
+        self._work = None          # the full batch, in original order
+        try:
+            pi = self.backward()
+        finally:
+            self._work, self.last_backward_sweeps = work, sweeps
+        ll, ll_traj, _ = ops.demo_log_likelihood(pi, torch.as_tensor(states, device=pi.device), actions, lengths)
+        return ll / ll_traj.shape[1]
+
+    @classmethod
+    def from_trajectories(cls, mdp, states, lengths, terminal, features=None, **kw):
+        """A BatchedMaxEnt whose demonstration statistics come from stored
+        trajectories (``states`` [B, N, L + 1], ``lengths`` [B, N]) through
+        ``ops.demo_statistics``: ``p_initial = starts / N`` and ``e_features =
+        visits / N`` (identity features), or ``(visits / N) @ F`` with a feature
+        matrix ``features`` ([S, F] or [B, S, F]) -- maxent.py:15-60.  Raises
+        ValueError if a trajectory holds a state off the model or a length
+        beyond its row.  ``kw``: the constructor's other arguments."""
+        visits, starts, status = ops.demo_statistics(mdp.n_states, torch.as_tensor(states, device=mdp.device), lengths)
+        bad = int((status != 0).sum())
+        if bad:
+            raise ValueError(f"from_trajectories: {bad} of {status.numel()} trajectories hold a state outside "
+                             f"[0, {mdp.n_states}) or a length outside their row")
+        n = status.shape[1]
+        e = visits.to(torch.float64) / n
+        if features is not None:
+            f = torch.as_tensor(features, dtype=torch.float64, device=e.device)
+            e = e @ f if f.dim() == 2 else torch.bmm(e.unsqueeze(1), f).squeeze(1)
+        return cls(mdp, e, starts.to(torch.float64) / n, terminal, features=features, **kw)
+
     def prime_compaction(self, eps=1e-4):
         """Run, once, every device operation of ``run()`` outside the passes --
         the stop test, ``compact()`` and ``update()`` on a working set, the

@@ -51,6 +51,54 @@ class TruncatedDemonstrations(ValueError):
     """Some trajectories were cut at ``max_len`` before reaching a terminal state."""
 
 
+def sample_device(mdp, terminal, start, n=200, seed=0, beta=2.0, max_len=None, on_truncate="raise"):
+    """Sample ``n`` demonstrations for every instance of a square STENCIL5
+    gridworld model at once, on the device (``ops.rollout``: one thread per
+    trajectory).
+
+    The expert is :func:`expert_policy` towards ``terminal[0]``, uploaded and
+    shared by the B instances; ``start`` is an int, ``[B]`` or ``[B, n]``;
+    ``seed`` an int or ``[B]`` 64-bit seeds (``ops.rollout_seeds``).  The device
+    call is always bounded: ``max_len=None`` means ``safety_cap(size)``.
+    Returns device tensors ``(e_features [B, S], p_initial [B, S], lengths
+    [B, n])``: float64 ``visits / n`` and ``starts / n`` (identity state
+    features, final states included) and int32 lengths.  Trajectories still alive
+    after ``max_len`` steps are cut under :func:`sample`'s rule
+    (``on_truncate="raise"`` raises TruncatedDemonstrations, ``"allow"`` keeps
+    them); a trajectory that met an invalid policy or table row or a start
+    state off the grid raises ValueError naming the status.
+
+    This sampler draws different random numbers from :func:`sample` (a
+    counter-based Philox stream per trajectory instead of numpy's generator in
+    lock-step), so the two give different demonstrations for the same seed;
+    :func:`sample` keeps its stream, which bench.py, the fixtures and the tests
+    depend on.  Input generation, outside any timed region.
+    """
+    import torch
+    from . import _lib, ops
+    if on_truncate not in ("raise", "allow"):
+        raise ValueError(f"on_truncate must be 'raise' or 'allow', got {on_truncate!r}")
+    if mdp.layout != _lib.LAYOUT_STENCIL5 or mdp.width != mdp.height or mdp.n_actions != 4:
+        raise ValueError("sample_device: square STENCIL5 gridworlds with the four move actions only")
+    size, S, B = mdp.width, mdp.n_states, mdp.batch
+    terminal = list(np.atleast_1d(terminal))
+    if max_len is None:
+        max_len = safety_cap(size)
+    pol = torch.as_tensor(expert_policy(size, terminal[0], beta), device=mdp.device)
+    out = ops.rollout(mdp, pol.unsqueeze(0).expand(B, S, 4), ops.terminal_mask(terminal, S, batch=B, device=mdp.device),
+                      start, n, max_len, seed)
+    status = out.status.cpu().numpy()
+    if (status >= _lib.TRAJ_BAD_POLICY).any():
+        worst = int(status.max())
+        raise ValueError(f"sample_device: {int((status == worst).sum())} of {status.size} demonstrations stopped with "
+                         f"status {worst} ({_lib.TRAJ_NAMES[worst]})")
+    truncated = int((status == _lib.TRAJ_TRUNCATED).sum())
+    if truncated and on_truncate == "raise":
+        raise TruncatedDemonstrations(f"{truncated} of {status.size} demonstrations did not reach a terminal state "
+                                      f"within max_len={max_len} steps (the reference samples until terminal)")
+    return out.visits.to(torch.float64) / n, out.starts.to(torch.float64) / n, out.lengths
+
+
 def sample(row_val, size, terminal, start, n=200, seed=0, beta=2.0, max_len=None, on_truncate="raise",
            with_truncated=False):
     """Sample ``n`` demonstrations on one STENCIL5 table ``row_val`` [4, 5, S].

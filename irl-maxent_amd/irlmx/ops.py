@@ -6,6 +6,7 @@ building blocks of the numpy drop-ins (``maxent``, ``solver``) and of the
 batched IRL driver (``irlmx.batch``).
 """
 
+import collections
 import os
 
 import numpy as np
@@ -363,6 +364,130 @@ def expected_value_difference(mdp, true_reward, p_action, p_initial, discount, t
     return (p0 * (v_opt - v_pi)).sum(dim=1), v_opt, v_pi
 
 
+RolloutResult = collections.namedtuple("RolloutResult", "visits starts lengths status states actions")
+
+
+def _i32(x, device, shape):
+    t = torch.as_tensor(x, device=device)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError(f"expected integers, got {t.dtype}")
+    return t.to(torch.int32).reshape(shape).contiguous()
+
+
+def rollout_seeds(seed, batch, device):
+    """The per-instance 64-bit seeds of :func:`rollout` as an int64 [B] device
+    tensor (the bits are what counts): an int s gives ``seed[b] = (s &
+    0xffffffff) | (b << 32)``; a sequence of B ints is taken as is, modulo 2^64."""
+    if np.ndim(seed) == 0 and not isinstance(seed, torch.Tensor):
+        s = [(int(seed) & 0xffffffff) | (b << 32) for b in range(batch)]
+    else:
+        s = [int(v) & 0xffffffffffffffff for v in (seed.tolist() if hasattr(seed, "tolist") else seed)]
+        if len(s) != batch:
+            raise ValueError(f"seed has {len(s)} entries for {batch} instances")
+    return torch.as_tensor(np.array(s, dtype=np.uint64).view(np.int64), device=device)
+
+
+def rollout(mdp, p_action, terminal, start, n, max_len, seed, return_trajectories=False):
+    """Sample ``n`` trajectories per instance under the policy ``p_action``
+    [B, S, A] on the device (irlmx_rollout), one thread per trajectory.
+
+    ``terminal``: a uint8 [B, S] mask (:func:`terminal_mask`).  ``start``: an
+    int, ``[B]`` or ``[B, n]`` start states.  ``max_len``: the step cap, 1 to
+    2^20.  ``seed``: an int s (``seed[b] = (s & 0xffffffff) | (b << 32)``) or
+    ``[B]`` 64-bit seeds; the random stream of trajectory i of an instance
+    depends on that instance's seed, i and the step only, so a caller that
+    shards or compacts a batch passes the seeds built from the original
+    instance ids and gets the same trajectories.
+
+    Returns ``RolloutResult(visits, starts, lengths, status, states, actions)``:
+    int64 [B, S] state visits (final states included) and start counts, int32
+    [B, n] lengths and ``_lib.TRAJ_*`` codes, and with ``return_trajectories``
+    int32 ``states`` [B, n, max_len + 1] and ``actions`` [B, n, max_len] holding
+    -1 beyond each trajectory's length (else None).  The same seeds give the
+    same bits on every run.  STENCIL5 and ELL models.
+    """
+    lib = _lib.load()
+    B, S, A, dev = mdp.batch, mdp.n_states, mdp.n_actions, mdp.device
+    n, max_len = int(n), int(max_len)
+    if n < 1:
+        raise ValueError(f"rollout: n={n} < 1")
+    pi = _f64(p_action, mdp, (B, S, A))
+    term = terminal.to(device=dev, dtype=torch.uint8).reshape(B, S).contiguous()
+    st = torch.as_tensor(start if isinstance(start, torch.Tensor) else np.array(start), device=dev)
+    if st.dim() < 2:
+        st = st.reshape(-1, 1).expand(B, n)
+    st = _i32(st, dev, (B, n))
+    seeds = rollout_seeds(seed, B, dev)
+    visits = torch.empty((B, S), dtype=torch.int64, device=dev)
+    starts = torch.empty((B, S), dtype=torch.int64, device=dev)
+    lengths = torch.empty((B, n), dtype=torch.int32, device=dev)
+    status = torch.empty((B, n), dtype=torch.int32, device=dev)
+    states = actions = None
+    if return_trajectories and 1 <= max_len <= _lib.ROLLOUT_MAX_LEN:
+        states = torch.full((B, n, max_len + 1), -1, dtype=torch.int32, device=dev)
+        actions = torch.full((B, n, max_len), -1, dtype=torch.int32, device=dev)
+    _lib.check(lib.irlmx_rollout(mdp.struct(), _lib.ptr(pi), _lib.ptr(term), _lib.ptr(st), _lib.ptr(seeds), n, max_len,
+                                 _lib.ptr(visits), _lib.ptr(starts), _lib.ptr(lengths), _lib.ptr(status),
+                                 _lib.ptr(states), _lib.ptr(actions), _lib.stream_ptr(dev)), "rollout")
+    return RolloutResult(visits, starts, lengths, status, states, actions)
+
+
+def _stored(states, lengths):
+    dev = _lib.require_device(states.device if isinstance(states, torch.Tensor) and states.is_cuda else None)
+    states = torch.as_tensor(states, device=dev)
+    if states.dim() != 3:
+        raise ValueError(f"states must be [B, N, L + 1], got {tuple(states.shape)}")
+    B, N, stride = states.shape
+    return dev, B, N, stride, _i32(states, dev, (B, N, stride)), _i32(lengths, dev, (B, N))
+
+
+def demo_statistics(n_states, states, lengths):
+    """``(visits [B, S] int64, starts [B, S] int64, status [B, N] int32)`` of
+    stored trajectories (irlmx_demo_statistics): ``states`` int [B, N, L + 1],
+    of which entries 0..lengths[b, n] are read.  ``visits / N`` and ``starts /
+    N`` are the reference's feature expectation with identity features and its
+    initial state distribution (maxent.py:15-60).  A trajectory with a state
+    outside [0, S) or a length outside [0, L] gets status ``_lib.TRAJ_BAD_INDEX``
+    and counts nothing."""
+    lib = _lib.load()
+    dev, B, N, stride, st, ln = _stored(states, lengths)
+    S = int(n_states)
+    visits = torch.empty((B, S), dtype=torch.int64, device=dev)
+    starts = torch.empty((B, S), dtype=torch.int64, device=dev)
+    status = torch.empty((B, N), dtype=torch.int32, device=dev)
+    _lib.check(lib.irlmx_demo_statistics(S, B, N, stride, _lib.ptr(st), _lib.ptr(ln), _lib.ptr(visits),
+                                         _lib.ptr(starts), _lib.ptr(status), _lib.stream_ptr(dev)), "demo_statistics")
+    return visits, starts, status
+
+
+def demo_log_likelihood(p_action, states, actions, lengths):
+    """Log-likelihood of stored demonstrations under the policy ``p_action``
+    [B, S, A] (irlmx_demo_log_likelihood): ``(ll [B], ll_traj [B, N], status
+    [B, N])`` with ``ll_traj[b, n] = sum_{t < len} log p_action[b, s_t, a_t]``
+    (numpy's log, added in step order) and ``ll[b]`` their sum in trajectory
+    order.  ``states`` [B, N, L + 1], ``actions`` [B, N, L], as :func:`rollout`
+    returns them.  A zero-probability action gives -inf; a trajectory with an
+    index out of range gets status ``_lib.TRAJ_BAD_INDEX`` and NaN."""
+    lib = _lib.load()
+    dev, B, N, stride, st, ln = _stored(states, lengths)
+    pi = torch.as_tensor(p_action, dtype=torch.float64, device=dev)
+    if pi.dim() != 3 or pi.shape[0] != B:
+        raise ValueError(f"p_action must be [B = {B}, S, A], got {tuple(pi.shape)}")
+    pi = pi.contiguous()
+    S, A = int(pi.shape[1]), int(pi.shape[2])
+    if stride > 1:
+        ac = _i32(actions, dev, (B, N, stride - 1))
+    else:
+        ac = torch.zeros(1, dtype=torch.int32, device=dev)   # no trajectory has a step: never read
+    ll = torch.empty(B, dtype=torch.float64, device=dev)
+    ll_traj = torch.empty((B, N), dtype=torch.float64, device=dev)
+    status = torch.empty((B, N), dtype=torch.int32, device=dev)
+    _lib.check(lib.irlmx_demo_log_likelihood(S, A, B, N, stride, _lib.ptr(pi), _lib.ptr(st), _lib.ptr(ac), _lib.ptr(ln),
+                                             _lib.ptr(ll_traj), _lib.ptr(ll), _lib.ptr(status), _lib.stream_ptr(dev)),
+               "demo_log_likelihood")
+    return ll, ll_traj, status
+
+
 def dense_gemm(m, z):
     """``z @ m.T`` on the fp64 matrix cores (irlmx_dense_gemm): m [R, S], z [B, S]
     float64 device tensors -> [B, R].  The batched P . [v_1 .. v_B] contraction
@@ -416,4 +541,5 @@ def stochastic_policy(successor, weighted_value):
 
 
 __all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "backward_maxent_extended", "forward_svf", "soft_backward",
-           "value_iteration", "policy_evaluation", "expected_value_difference", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]
+           "value_iteration", "policy_evaluation", "expected_value_difference", "rollout", "rollout_seeds",
+           "demo_statistics", "demo_log_likelihood", "RolloutResult", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]

@@ -25,7 +25,11 @@
 //    per sweep, never a persistent shape), its refusal of DENSE tables and of
 //    the backward-only flags, and every validation path of
 //    irlmx_policy_evaluation (NULL arrays, discount outside [0, 1] or NaN,
-//    short workspace).
+//    short workspace);
+//  * the demonstration calls (rollout.hip): every validation path of
+//    irlmx_rollout (NULL arrays, n_traj, max_len below 1 and above its cap,
+//    states without actions, DENSE tables), irlmx_demo_statistics and
+//    irlmx_demo_log_likelihood (sizes, stride, NULL arrays).
 //
 // Exit status 0 and "host_check ok" on success.
 
@@ -275,6 +279,13 @@ static int run_pe(const irlmx_mdp* m, void* reward, void* pi, void* term, double
                                  (double*)value, (int64_t*)iters, (int32_t*)status, ws, n, nullptr);
 }
 
+static int run_roll(const irlmx_mdp* m, int n_traj, int max_len, void* pi, void* term, void* start, void* seed,
+                    void* visits, void* starts, void* lengths, void* status, void* states, void* actions) {
+  return irlmx_rollout(m, (const double*)pi, (const uint8_t*)term, (const int32_t*)start, (const uint64_t*)seed, n_traj,
+                       max_len, (int64_t*)visits, (int64_t*)starts, (int32_t*)lengths, (int32_t*)status,
+                       (int32_t*)states, (int32_t*)actions, nullptr);
+}
+
 static void expect(int rc, int want, const char* msg_part, const char* what) {
   CHECK(rc == want, "%s: rc %d, want %d (%s)", what, rc, want, irlmx_last_error());
   CHECK(strstr(irlmx_last_error(), msg_part) != nullptr, "%s: message '%s' lacks '%s'", what, irlmx_last_error(),
@@ -375,6 +386,69 @@ static void error_paths() {
     CHECK(p[0] == IRLMX_SHAPE_SWEEP, "policy evaluation plan K = 40: shape %lld", (long long)p[0]);
     expect(irlmx_execution_plan(&good, IRLMX_OP_POLICY_EVALUATION + 1, p), IRLMX_EINVAL, "unknown op 7", "op 7");
     expect(irlmx_execution_plan(&good, 5, p), IRLMX_EINVAL, "unknown op 5", "op 5 (never an op)");
+  }
+  {  // irlmx_rollout, irlmx_demo_statistics, irlmx_demo_log_likelihood: every validation path
+    expect(run_roll(nullptr, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "mdp is NULL", "rollout null mdp");
+    for (const Bad& b : bad) expect(run_roll(&b.m, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, b.msg, b.name);
+    irlmx_mdp d = dense(25, 4, 1);
+    expect(run_roll(&d, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "rollout: ", "rollout dense");
+    expect(run_roll(&d, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "DENSE", "rollout dense");
+    const char* names[8] = {"p_action", "terminal", "start", "seed", "visits", "starts", "lengths", "traj_status"};
+    for (int i = 0; i < 8; ++i) {
+      void* a[8] = {f, f, f, f, f, f, f, f};
+      a[i] = nullptr;
+      char msg[64];
+      snprintf(msg, sizeof(msg), "rollout: %s is NULL", names[i]);
+      expect(run_roll(&good, 8, 16, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], f, f), IRLMX_EINVAL, msg, msg);
+    }
+    expect(run_roll(&good, 0, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "n_traj=0 < 1", "rollout n_traj 0");
+    expect(run_roll(&good, 8, 0, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "max_len=0 outside [1, 1048576]",
+           "rollout max_len 0");
+    expect(run_roll(&good, 8, (1 << 20) + 1, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "max_len=1048577 outside",
+           "rollout max_len above the cap");
+    expect(run_roll(&good, 8, 16, f, f, f, f, f, f, f, f, f, nullptr), IRLMX_EINVAL, "both be NULL or both be set",
+           "rollout states without actions");
+    expect(run_roll(&good, 8, 16, f, f, f, f, f, f, f, f, nullptr, f), IRLMX_EINVAL, "both be NULL or both be set",
+           "rollout actions without states");
+    int32_t* i32 = (int32_t*)f;
+    int64_t* i64 = (int64_t*)f;
+    double* dbl = (double*)f;
+    expect(irlmx_demo_statistics(0, 1, 8, 17, i32, i32, i64, i64, i32, nullptr), IRLMX_EINVAL, "demo_statistics: bad sizes",
+           "statistics S = 0");
+    expect(irlmx_demo_statistics(25, 1, 0, 17, i32, i32, i64, i64, i32, nullptr), IRLMX_EINVAL, "n_traj=0 < 1",
+           "statistics n_traj 0");
+    expect(irlmx_demo_statistics(25, 1, 8, 0, i32, i32, i64, i64, i32, nullptr), IRLMX_EINVAL, "stride=0 < 1",
+           "statistics stride 0");
+    expect(irlmx_demo_statistics(25, 1, 8, 17, nullptr, i32, i64, i64, i32, nullptr), IRLMX_EINVAL,
+           "demo_statistics: states is NULL", "statistics null states");
+    expect(irlmx_demo_statistics(25, 1, 8, 17, i32, nullptr, i64, i64, i32, nullptr), IRLMX_EINVAL, "lengths is NULL",
+           "statistics null lengths");
+    expect(irlmx_demo_statistics(25, 1, 8, 17, i32, i32, nullptr, i64, i32, nullptr), IRLMX_EINVAL, "visits is NULL",
+           "statistics null visits");
+    expect(irlmx_demo_statistics(25, 1, 8, 17, i32, i32, i64, nullptr, i32, nullptr), IRLMX_EINVAL, "starts is NULL",
+           "statistics null starts");
+    expect(irlmx_demo_statistics(25, 1, 8, 17, i32, i32, i64, i64, nullptr, nullptr), IRLMX_EINVAL, "traj_status is NULL",
+           "statistics null status");
+    expect(irlmx_demo_log_likelihood(25, 0, 1, 8, 17, dbl, i32, i32, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "demo_log_likelihood: bad sizes", "likelihood A = 0");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, -2, 17, dbl, i32, i32, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "n_traj=-2 < 1", "likelihood n_traj < 0");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 0, dbl, i32, i32, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "stride=0 < 1", "likelihood stride 0");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 17, nullptr, i32, i32, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "demo_log_likelihood: p_action is NULL", "likelihood null p_action");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 17, dbl, nullptr, i32, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "states is NULL", "likelihood null states");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 17, dbl, i32, nullptr, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "actions is NULL", "likelihood null actions");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 17, dbl, i32, i32, nullptr, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "lengths is NULL", "likelihood null lengths");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 17, dbl, i32, i32, i32, nullptr, dbl, i32, nullptr), IRLMX_EINVAL,
+           "ll_traj is NULL", "likelihood null ll_traj");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 17, dbl, i32, i32, i32, dbl, nullptr, i32, nullptr), IRLMX_EINVAL,
+           "ll is NULL", "likelihood null ll");
+    expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 17, dbl, i32, i32, i32, dbl, dbl, nullptr, nullptr), IRLMX_EINVAL,
+           "traj_status is NULL", "likelihood null status");
   }
   expect(irlmx_forward_svf(&good, (double*)f, (uint8_t*)f, (double*)f, 1e-5, 0, (double*)f, nullptr, (int32_t*)f, f,
                            1 << 30, nullptr),
