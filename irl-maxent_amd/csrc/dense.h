@@ -1,5 +1,5 @@
 // Dense-row path (IRLMX_LAYOUT_DENSE): shared declarations between dense.hip
-// (kernels) and fixed_point.hip (the per-sweep drivers and the C ABI).
+// (kernels) and fixed_point.hip (the route, the per-sweep drivers and the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,7 +16,7 @@ struct DenseView {
   const double* M;  // [B'][S][S]:    sum_a P[s, t, a]
 };
 
-// Per-sweep state, the same conventions as the sweep shape (fixed_point.hip Ws):
+// Per-sweep state, the same conventions as the sweep shape (fixed_point.h Ws):
 // ping-pong vectors, a 3-slot ring of per-instance max|.| words, done flags.
 struct DenseBufs {
   double* buf0;               // [B][S]

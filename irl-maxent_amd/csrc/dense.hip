@@ -17,7 +17,7 @@
 // or the stacked P_a for soft VI / VI); fixed_point.hip then runs it on the
 // hand-written fp64 MFMA kernel below plus an epilogue, or streams M once per
 // instance -- whichever the planner's measured crossover picks (dense_gemm()
-// in fixed_point.hip: from 16 instances, from 4 at S >= 4096).  Up to S = 2048
+// in fixed_point.hip, read through its route(): from 16 instances, from 4 at S >= 4096).  Up to S = 2048
 // the persistent dense shape (dense_grid.hip) takes the calls the GEMM does not.
 // Convergence bookkeeping follows the sweep shape of fixed_point.hip (3-slot
 // max ring, done flags, host polling).
@@ -38,7 +38,7 @@ __device__ inline int dense_finish_status(double delta, double eps) {
   return delta > eps ? IRLMX_MAXITER : IRLMX_OK;
 }
 
-// The reference's loop test for instance b before sweep `it` (fixed_point.hip
+// The reference's loop test for instance b before sweep `it` (fixed_point.h
 // sweep_should_stop): stop after the first sweep whose max|delta| is not > eps.
 __device__ inline bool dense_should_stop(int b, long long it, int r3, double eps, long long max_iter,
                                          const DenseBufs& w, int32_t* status) {

@@ -1,7 +1,8 @@
-// Model views, the workspace, the stopping-rule helpers and the host helpers of
-// the fixed-point passes that more than one translation unit uses
-// (fixed_point.hip defines the host functions; extended.hip and
-// policy_eval.hip are the other users).
+// Model views, the workspace, the stopping-rule helpers, the argument struct
+// of the Bellman kernels and the host helpers of the fixed-point passes that
+// more than one translation unit uses (fixed_point.hip defines the host
+// functions; grid.hip, numpy_order.hip, extended.hip and policy_eval.hip are
+// the other users).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -104,6 +105,22 @@ struct Ws {
 Ws carve(const Model& m, int op, void* base);
 // IRLMX_EWORKSPACE and the message unless `bytes` at `ws` hold carve(m, op).total.
 int check_ws(const Model& m, int op, size_t bytes, void* ws);
+
+// Arguments of the soft VI / VI kernels of every shape (fixed_point.hip fused
+// and per sweep, grid.hip, numpy_order.hip).
+struct SoftArgs {
+  Model m;
+  const double* reward;
+  const double* phi;  // soft: terminal reward; unused by VI
+  double discount;
+  double eps;
+  long long max_iter;
+  int average;  // VI only
+  double* pi;   // soft only, [B][S][A]
+  double* value;
+  int64_t* iters;
+  int32_t* status;
+};
 
 // ---------------------------------------------------------------------------
 // the stopping rule, fused shape

@@ -75,7 +75,7 @@ OPS = ("backward", "forward", "soft_backward", "value_iteration")
 _ = None   # one launch per sweep
 #: The fused instantiation <SPT, KMAX> each pass of each case reaches on the
 #: default plan, None for the per-sweep shape: written out by hand, derived
-#: from fused_shape / fused_pair_ok (csrc/fixed_point.hip).  plan() below restates
+#: from fused_shape / fused_pair_ok (csrc/fixed_point.hip, .h).  plan() below restates
 #: the planner; tests/test_ell_cases.py holds the two against each other, the GPU
 #: test holds the device's plan against this table.
 FUSED = {
@@ -99,7 +99,7 @@ GRID = {
     "k40-s300": (_, _, _, _),
 }
 
-# -- the planner, restated (csrc/fixed_point.hip: pick_kmax, fused_pair_ok, fused_shape, grid_plan;
+# -- the planner, restated (csrc/fixed_point.hip: pick_kmax, fused_pair_ok, fused_shape; csrc/grid.hip: grid_plan;
 #    csrc/extended.hip: ext_pair_ok is the backward's list) ----------------------------------
 
 FUSED_MAX_STATES, MAX_ACTIONS, GRID_MAX_ACTIONS, GRID_THREADS, WAVE = 4096, 8, 5, 256, 64

@@ -9,8 +9,9 @@
 // ever enqueued.  What it exercises under the sanitizers:
 //
 //  * the tile planner (cluster.hip cluster_plan: R / G / C / states per lane /
-//    LDS budget), the fused / grid / dense shape choice and the workspace
-//    carving (fixed_point.hip carve) for widths 5..256, rectangular grids,
+//    LDS budget), the grid planner (grid.hip grid_plan), the choice of shape
+//    (fixed_point.hip route) and the workspace carving it sizes
+//    (fixed_point.hip carve) for widths 5..256, rectangular grids,
 //    batches 1..256, all four ops, stencil / ELL / DENSE layouts -- through the
 //    C ABI's irlmx_execution_plan and irlmx_workspace_bytes, with invariants
 //    checked on every plan;
@@ -32,6 +33,10 @@
 //    irlmx_demo_log_likelihood (sizes, stride, NULL arrays).
 //
 // Exit status 0 and "host_check ok" on success.
+//
+// host_check --dump checks nothing: it prints the plan and the workspace size of
+// every model and op of that sweep (dump_plans), to compare two builds of the
+// library -- before and after a change to the planners -- byte for byte.
 
 #include <cstdint>
 #include <cstdio>
@@ -490,30 +495,27 @@ static void error_paths() {
   CHECK(irlmx_counters(nullptr, 3) == IRLMX_COUNTERS_LEN, "counters length (NULL)");
 }
 
-int main() {
-  setenv("IRLMX_PLAN_CUS", "256", 1);          // the MI355X's CU count, without a device
-  setenv("IRLMX_PLAN_GRID_PER_CU", "4", 1);
-  CHECK(irlmx_abi_version() == IRLMX_ABI_VERSION, "abi version");
-  error_paths();
-
+// The models of the planner sweep, each handed to f(model, tag); returns their number.
+template <class F>
+static long long for_each_model(F&& f) {
   std::vector<int> widths, batches;
   for (int w = 5; w <= 40; ++w) widths.push_back(w);
   for (int w = 41; w <= 256; w += 9) widths.push_back(w);
   for (int w : {48, 63, 64, 65, 96, 127, 128, 129, 192, 255, 256}) widths.push_back(w);
   for (int b = 1; b <= 16; ++b) batches.push_back(b);
   for (int b : {17, 31, 32, 33, 63, 64, 65, 100, 127, 128, 129, 200, 255, 256}) batches.push_back(b);
-  long long plans = 0;
+  long long models = 0;
   for (int w : widths) {
     for (int b : batches) {
       for (int shared = 0; shared <= 1; ++shared) {
-        plan_and_workspace(stencil(w, w, 4, b, shared), "square");
-        plan_and_workspace(stencil(w, w, 5, b, shared), "square A=5");
-        plans += 8;
+        f(stencil(w, w, 4, b, shared), "square");
+        f(stencil(w, w, 5, b, shared), "square A=5");
+        models += 2;
       }
       if (w % 3 == 0) {  // rectangles: wide and tall
-        plan_and_workspace(stencil(w, 2 * w + 1, 4, b, 0), "tall");
-        plan_and_workspace(stencil(2 * w, w, 4, b, 0), "wide");
-        plans += 8;
+        f(stencil(w, 2 * w + 1, 4, b, 0), "tall");
+        f(stencil(2 * w, w, 4, b, 0), "wide");
+        models += 2;
       }
     }
   }
@@ -522,17 +524,65 @@ int main() {
     for (int k : {1, 2, 5, 8, 9, 16, 17, 32, 33}) {
       if (k > s) continue;
       for (int b : {1, 3, 16, 64, 256}) {
-        plan_and_workspace(ell(s, 4, k, k, b), "ell");
-        plan_and_workspace(ell(s, 4, k, (k % 5) + 1, b), "ell skew");
-        plans += 8;
+        f(ell(s, 4, k, k, b), "ell");
+        f(ell(s, 4, k, (k % 5) + 1, b), "ell skew");
+        models += 2;
       }
     }
   }
   for (int s : {7, 64, 301, 1040, 2048, 4096, 8192})
     for (int b : {1, 3, 4, 15, 16, 17, 64}) {
-      plan_and_workspace(dense(s, 4, b), "dense");
-      plans += 4;
+      f(dense(s, 4, b), "dense");
+      ++models;
     }
+  return models;
+}
+
+// --dump: for every model of the sweep and every op (the four passes, the
+// backward with IRLMX_PLAN_NO_RESCALE and with IRLMX_PLAN_EXTENDED_RANGE, policy
+// evaluation) one line with the plan's return code, plan[0..9] and the
+// workspace bytes -- first with the planner's defaults, then with each of its
+// shape switches set alone.  Two libraries that print the same text plan and
+// size every call of the sweep alike.
+static void dump_plans() {
+  const char* const switches[][2] = {{nullptr, nullptr},
+                                     {"IRLMX_FUSED_MAX_STATES", "0"},
+                                     {"IRLMX_CLUSTER", "0"},
+                                     {"IRLMX_GRID", "0"},
+                                     {"IRLMX_DENSE_GEMM_MIN", "1"}};
+  const int ops[] = {IRLMX_OP_BACKWARD, IRLMX_OP_FORWARD, IRLMX_OP_SOFT_BACKWARD, IRLMX_OP_VALUE_ITERATION,
+                     IRLMX_OP_BACKWARD | IRLMX_PLAN_NO_RESCALE, IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE,
+                     IRLMX_OP_POLICY_EVALUATION};
+  for (const auto& sw : switches) {
+    if (sw[0]) setenv(sw[0], sw[1], 1);
+    for_each_model([&](const irlmx_mdp& m, const char* tag) {
+      for (int op : ops) {
+        int64_t p[IRLMX_PLAN_LEN];
+        for (auto& v : p) v = -7;
+        const int rc = irlmx_execution_plan(&m, op, p);
+        printf("%s=%s %s %dx%d S %d A %d K %d/%d B %d shared %d op %#x: rc %d plan", sw[0] ? sw[0] : "default",
+               sw[0] ? sw[1] : "", tag, m.width, m.height, m.n_states, m.n_actions, m.k_row, m.k_col, m.batch, m.shared,
+               op, rc);
+        for (int64_t v : p) printf(" %lld", (long long)v);
+        // (workspace_bytes takes no IRLMX_PLAN_NO_RESCALE: the backward's workspace serves both)
+        printf(" ws %zu\n", irlmx_workspace_bytes(&m, op & ~IRLMX_PLAN_NO_RESCALE));
+      }
+    });
+    if (sw[0]) unsetenv(sw[0]);
+  }
+}
+
+int main(int argc, char** argv) {
+  setenv("IRLMX_PLAN_CUS", "256", 1);          // the MI355X's CU count, without a device
+  setenv("IRLMX_PLAN_GRID_PER_CU", "4", 1);
+  if (argc > 1 && strcmp(argv[1], "--dump") == 0) {
+    dump_plans();
+    return 0;
+  }
+  CHECK(irlmx_abi_version() == IRLMX_ABI_VERSION, "abi version");
+  error_paths();
+
+  const long long plans = 4 * for_each_model([](const irlmx_mdp& m, const char* tag) { plan_and_workspace(m, tag); });
   if (g_fail) {
     fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
     return 1;
