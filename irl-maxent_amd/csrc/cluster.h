@@ -40,6 +40,7 @@ static_assert(kSumSlots > kRescaleEvery, "summary slots must outlast the rescale
 constexpr int kSumRows = kSumSlots + 2;
 constexpr int kXccRow = kSumSlots, kFullRow = kSumSlots + 1;
 constexpr size_t kClusterStaticLds = 128;     // cluster_kernel's own __shared__ variables (resident flag, stamps)
+constexpr int kStampWords = 10;  // ClusterArgs::stamps record per workgroup (cluster.hip, stamp_flush)
 constexpr int kModeFwd = 0;
 constexpr int kModeBwd = 1;
 
@@ -71,7 +72,7 @@ struct ClusterArgs {
   int test_drop;           // tests only (IRLMX_TEST_DROP_TILE): this workgroup leaves after the rendezvous, else -1
   int eager_summary;       // A/B and tests (IRLMX_EAGER_SUMMARY=1): wait for every tile's summary every block
   int trap_noskip;         // A/B and tests (IRLMX_TRAP_NOSKIP=1): the trapezoid layout (cluster.hip) sweeping every row
-  unsigned long long* stamps;  // optional [grid][8] phase cycle counters (IRLMX_STAMPS=1), else null
+  unsigned long long* stamps;  // optional [grid][kStampWords] phase cycle and polling-pass counters (IRLMX_STAMPS=1), else null
   double* out;             // forward: svf [B][S]; backward: pi [B][S][A]
   int64_t* iters;
   int32_t* status;
@@ -147,13 +148,18 @@ __device__ inline void gran_store(const Gran& g, unsigned off, unsigned long lon
 // Poll the granule pairs selected by `want` (bit k: entry k; the last entry
 // through rsrc `rl`, the others through `r`) until all carry `tag`; false
 // after `limit` ticks of s_memrealtime (100 MHz; default 20 s).  Every pending
-// load of a pass is in flight at once.
+// load of a pass is in flight at once.  Diagnostics: a lane with `count` set
+// and `passes` not null adds its passes to that LDS counter (the caller selects
+// the lane by either argument, cluster.hip; a count kept in a register of
+// every lane cost config 3's backward 0.4-0.8 ms of 22,
+// profiles/gather_overlap_ab.txt).
 constexpr unsigned long long kGatherTicks = 2000000000ull;
 // (mask type M: 32-bit, or 64-bit for more than 32 entries)
 template <int N, typename M>
 __device__ inline bool gran_gather(const Gran& r, const Gran& rl, const unsigned (&off)[N],
                                    M want, unsigned tag, unsigned long long (&v)[N],
-                                   unsigned long long limit = kGatherTicks) {
+                                   unsigned long long limit = kGatherTicks, unsigned long long* passes = nullptr,
+                                   bool count = true) {
   static_assert(N <= 8 * (int)sizeof(M), "gran_gather: mask too narrow");
   M pending = want;
 #if IRLMX_DEVICE_CHECKS
@@ -172,6 +178,7 @@ __device__ inline bool gran_gather(const Gran& r, const Gran& rl, const unsigned
     for (int k = 0; k < N; ++k)
       if ((pending >> k) & 1u)
         x[k] = __builtin_amdgcn_raw_buffer_load_b128(k == N - 1 ? rl.r : r.r, (int)off[k], 0, 16 /* sc1 */);
+    if (count && passes) *passes += 1ull;  // (while the loads are in flight)
 #pragma unroll
     for (int k = 0; k < N; ++k)
       if (((pending >> k) & 1u) && x[k].y == tag && x[k].w == tag) {

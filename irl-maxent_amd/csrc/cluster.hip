@@ -896,10 +896,13 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   // phase cycle counters (thread 0): sweeps, summary + publish, exchange wait, refresh, blocks
   // (in LDS, thread 0 only: as registers they are live across the sweep loop and
   // push the quad kernels over their register budget)
-  __shared__ unsigned long long st_acc[8], ts_l[1];  // st_acc[5], [6]: sub-phases of 1
+  // st_acc[5], [6]: sub-phases of 1; [7], [8]: thread 0's polling passes of the
+  // per-block gather, summed over the blocks and the most in one block ([9]:
+  // the current block's, counted in gran_gather)
+  __shared__ unsigned long long st_acc[10], ts_l[1];
   const bool stamps = a.stamps != nullptr && tid == 0;
   if (stamps) {
-    for (int k = 0; k < 8; ++k) st_acc[k] = 0ull;
+    for (int k = 0; k < 10; ++k) st_acc[k] = 0ull;
     ts_l[0] = stamp_now();
   }
   unsigned long long& ts = ts_l[0];
@@ -908,10 +911,10 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
   };
   auto stamp_flush = [&]() {
     if (stamps) {
-      for (int k = 0; k < 5; ++k) a.stamps[(size_t)lin * 8 + k] = st_acc[k];
-      a.stamps[(size_t)lin * 8 + 5] = plain ? 1 : 0;
-      a.stamps[(size_t)lin * 8 + 6] = st_acc[5];
-      a.stamps[(size_t)lin * 8 + 7] = st_acc[6];
+      unsigned long long* rec = a.stamps + (size_t)lin * kStampWords;
+      for (int k = 0; k < 5; ++k) rec[k] = st_acc[k];
+      rec[5] = plain ? 1 : 0;
+      for (int k = 6; k < kStampWords; ++k) rec[k] = st_acc[k - 1];
     }
   };
   const long long total = MODE == kModeBwd ? a.n_sweeps : -1;
@@ -1135,7 +1138,13 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
         off[GPT] = ((unsigned)(m % kSumSlots) * (unsigned)a.H + (unsigned)tid) * 16u;
         want |= (k0 == 0 && tid < a.C && need_summary ? 1u : 0u) << GPT;
         unsigned long long v[GPT + 1];
-        ok &= gran_gather<GPT + 1>(rg, rs, off, want, tag, v, a.gather_ticks);
+        // (pass counter of the stamps: thread 0 is selected by a null pointer in
+        // the other lanes in the backward and by a flag in the forward -- the
+        // kernels at 256 VGPRs spill more than tests/test_kernel_resources.py
+        // allows with the other form: the forward's with the pointer, a lane
+        // value held through the loop, the backward's column quads with the flag)
+        if (MODE == kModeBwd) ok &= gran_gather<GPT + 1>(rg, rs, off, want, tag, v, a.gather_ticks, stamps ? &st_acc[9] : nullptr);
+        else ok &= gran_gather<GPT + 1>(rg, rs, off, want, tag, v, a.gather_ticks, &st_acc[9], stamps);
 #pragma unroll
         for (int i = 0; i < GPT; ++i)
           if ((want >> i) & 1u) cur[pad + ls[i]] = bits_double(v[i]);
@@ -1143,6 +1152,11 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
           if (MODE == kModeFwd) atomicOr(&red32[2 + (m & 1)], (unsigned)v[GPT]);
           else atomicMax(&red32[2 + (m & 1)], (unsigned)v[GPT]);
         }
+      }
+      if (stamps) {  // st_acc[9]: this block's passes
+        st_acc[7] += st_acc[9];
+        if (st_acc[9] > st_acc[8]) st_acc[8] = st_acc[9];
+        st_acc[9] = 0ull;
       }
     };
     if (!solo) gather();
@@ -1241,7 +1255,9 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     }
     done += Tm;
     // ---- rescale (backward), snapshot (forward), register copy (pair) --------
-    const int e_scale = resc ? code_exponent(summary) : 0;
+    // (wave-uniform -- every lane read the same LDS word -- and held in a scalar
+    // register, so the rescale below is one scalar branch)
+    const int e_scale = resc ? __builtin_amdgcn_readfirstlane(code_exponent(summary)) : 0;
     if (MODE == kModeBwd) rescale_in = resc ? ((e_scale <= 0 && m >= 3) ? p_max : 1) : rescale_in - 1;
     if constexpr (PAIR) {
       const unsigned ob = slot_bits(own_bits), xb = slot_bits(ext_bits);
@@ -1251,14 +1267,25 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
         const bool own = (ob >> (2 * jp)) & 1u, ext = (xb >> (2 * jp)) & 1u;
         double2 v = make_double2(cv[PAIR ? 2 * jp : 0], cv[PAIR ? 2 * jp + 1 : 0]);
         if (!own && ext) v = *reinterpret_cast<const double2*>(cur + pad + l);  // gathered ghost pair
-        if (MODE == kModeBwd && e_scale) {
-          v.x = ldexp(v.x, e_scale);
-          v.y = ldexp(v.y, e_scale);
-          if (ext && !COLS) *reinterpret_cast<double2*>(cur + pad + l) = v;
-        }
         if (MODE == kModeFwd && ext && !COLS) *reinterpret_cast<double2*>(snap + l) = v;  // COLS: in the first sweep
         cv[PAIR ? 2 * jp : 0] = v.x;
         cv[PAIR ? 2 * jp + 1 : 0] = v.y;
+      }
+      // Backward, blocks with a nonzero rescale exponent only (one in
+      // kRescaleEvery once the vector grows): every slot times 2^e_scale,
+      // behind one wave-uniform branch; the other blocks only merged the
+      // gathered ghost pairs above.  Written inside that loop, the 14 ldexp and
+      // their 28 selects ran in every block of config 3's backward, right after
+      // the barrier below: 1.4k of its 12.6k cycles per block (DESIGN.md
+      // section 5, profiles/gather_overlap_ab.txt).
+      if (MODE == kModeBwd && e_scale) {
+#pragma unroll
+        for (int jp = 0; jp < NS / 2; ++jp) {
+          const double2 v = make_double2(ldexp(cv[PAIR ? 2 * jp : 0], e_scale), ldexp(cv[PAIR ? 2 * jp + 1 : 0], e_scale));
+          if (!COLS && ((xb >> (2 * jp)) & 1u)) *reinterpret_cast<double2*>(cur + pad + slot_state(2 * jp)) = v;
+          cv[PAIR ? 2 * jp : 0] = v.x;
+          cv[PAIR ? 2 * jp + 1 : 0] = v.y;
+        }
       }
     } else if (MODE == kModeFwd || e_scale) {
       for (int l = tid; l < E; l += NT) {
@@ -1625,9 +1652,9 @@ int cluster_run(int mode, const ClusterPlan& plan, ClusterArgs a, int B, hipStre
   unsigned long long* stamps = nullptr;
   const int nwg = p.C * std::min(p.per_launch, B);
   if (env_int("IRLMX_STAMPS", 0)) {  // diagnostics only: phase cycle counters per workgroup
-    e = hipMallocAsync((void**)&stamps, sizeof(unsigned long long) * 8 * nwg, st);
+    e = hipMallocAsync((void**)&stamps, sizeof(unsigned long long) * kStampWords * nwg, st);
     if (e != hipSuccess) return hip_fail(e, "stamps alloc");
-    (void)hipMemsetAsync(stamps, 0, sizeof(unsigned long long) * 8 * nwg, st);
+    (void)hipMemsetAsync(stamps, 0, sizeof(unsigned long long) * kStampWords * nwg, st);
   }
   a.stamps = stamps;
   const LaunchTestKnobs tk = launch_test_knobs();  // tests only (cluster.h)
@@ -1657,24 +1684,33 @@ int cluster_run(int mode, const ClusterPlan& plan, ClusterArgs a, int B, hipStre
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return hip_fail(e, "cluster sync");
   if (stamps) {
-    unsigned long long* h = (unsigned long long*)malloc(sizeof(unsigned long long) * 8 * nwg);
-    (void)hipMemcpy(h, stamps, sizeof(unsigned long long) * 8 * nwg, hipMemcpyDeviceToHost);
-    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int g = 0; g < nwg; ++g)
-      for (int k = 0; k < 8; ++k) acc[k] += (double)h[(size_t)g * 8 + k] / nwg;
+    unsigned long long* h = (unsigned long long*)malloc(sizeof(unsigned long long) * kStampWords * nwg);
+    (void)hipMemcpy(h, stamps, sizeof(unsigned long long) * kStampWords * nwg, hipMemcpyDeviceToHost);
+    double acc[kStampWords] = {};
+    unsigned long long pmax = 0;  // most polling passes thread 0 of any workgroup needed in one block
+    for (int g = 0; g < nwg; ++g) {
+      for (int k = 0; k < kStampWords; ++k) acc[k] += (double)h[(size_t)g * kStampWords + k] / nwg;
+      pmax = std::max(pmax, h[(size_t)g * kStampWords + 9]);
+    }
     fprintf(stderr, "[irlmx stamps] %s%s mode=%d R=%d G=%d C=%d spt=%d blocks=%.0f  cycles/block: sweeps %.0f  publish %.0f  "
-                    "wait %.0f  refresh %.0f  same-xcd %.2f  (publish: stores %.0f, summary %.0f)\n", "lds", p.pair == 4 ? "-quads-cw" : p.pair == 3 ? "-quads" : (p.pair == 2 ? "-cols" : (p.pair == 1 ? "-pair" : "")), mode, p.R, p.G, p.C, p.spt,
+                    "wait %.0f  refresh %.0f  same-xcd %.2f  (publish: stores %.0f, summary %.0f)  "
+                    "passes/block: mean %.2f  max %llu\n", "lds", p.pair == 4 ? "-quads-cw" : p.pair == 3 ? "-quads" : (p.pair == 2 ? "-cols" : (p.pair == 1 ? "-pair" : "")), mode, p.R, p.G, p.C, p.spt,
             acc[4], acc[0] / acc[4], acc[1] / acc[4], acc[2] / acc[4], acc[3] / acc[4], acc[5], acc[6] / acc[4],
-            (acc[7] - acc[6]) / acc[4]);
+            (acc[7] - acc[6]) / acc[4], acc[8] / acc[4], pmax);
     if (p.C <= 8) {  // per tile position: the interior tiles carry ghost rows on both sides
       for (int t = 0; t < p.C; ++t) {
-        double ta[5] = {0, 0, 0, 0, 0};
+        double ta[6] = {0, 0, 0, 0, 0, 0};
+        unsigned long long tmax = 0;
         int n = 0;
-        for (int g = t; g < nwg; g += p.C, ++n)
-          for (int k = 0; k < 5; ++k) ta[k] += (double)h[(size_t)g * 8 + k];
+        for (int g = t; g < nwg; g += p.C, ++n) {
+          const unsigned long long* rec = h + (size_t)g * kStampWords;
+          for (int k = 0; k < 5; ++k) ta[k] += (double)rec[k];
+          ta[5] += (double)rec[8];
+          tmax = std::max(tmax, rec[9]);
+        }
         if (n && ta[4] > 0)
-          fprintf(stderr, "[irlmx stamps]   tile %d: sweeps %.0f  publish %.0f  wait %.0f  refresh %.0f\n", t,
-                  ta[0] / ta[4], ta[1] / ta[4], ta[2] / ta[4], ta[3] / ta[4]);
+          fprintf(stderr, "[irlmx stamps]   tile %d: sweeps %.0f  publish %.0f  wait %.0f  refresh %.0f  passes %.2f (max %llu)\n", t,
+                  ta[0] / ta[4], ta[1] / ta[4], ta[2] / ta[4], ta[3] / ta[4], ta[5] / ta[4], tmax);
       }
     }
     free(h);
