@@ -186,13 +186,28 @@ int irlmx_backward_maxent(const irlmx_mdp* mdp, const double* reward, const uint
  * contrast of 4 on a grid 256 wide is enough).  Same weights, slot order and
  * fused multiply-adds as irlmx_backward_maxent: bit-identical to it (rescale
  * != 0) wherever that pass neither underflows nor overflows.  Exactly 2*S
- * sweeps; fully asynchronous on `stream`.  Non-finite exp(reward) gives an
+ * sweeps; fully asynchronous on `stream` on the fused and per-sweep shapes
+ * (on the grid shape, below, the call synchronises `stream`: each launch's
+ * outcome is read on the host).  Non-finite exp(reward) gives an
  * all-NaN policy for that instance; a state that cannot reach a terminal 0 / 0
  * = NaN, as in the reference.  STENCIL5 and ELL layouts, S <= 2^19;
  * IRLMX_EINVAL for DENSE.  Workspace: irlmx_workspace_bytes(mdp,
- * IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE).  Models above 4096 states
- * run one launch per sweep (2*S - 1 launches: correct, and slow at config-4
- * size); there is no persistent multi-CU form of this pass.
+ * IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE).  Three shapes, in this
+ * order.  Fused: up to 4096 states, one workgroup per instance.  Grid: from
+ * 8192 states on (an absolute floor, whatever IRLMX_FUSED_MAX_STATES says;
+ * IRLMX_EXT_GRID_MIN_STATES moves it, tests use 0), models of at most 16
+ * slots per state whose instance fits 256 workgroups of 256 threads with 1, 2
+ * or 4 states per thread (S <= 2^18): one persistent launch runs all 2*S
+ * sweeps of as many instances as can be co-resident, every partition value
+ * exchanged per sweep as two tagged granules (mantissa, exponent); a batch
+ * larger than that takes ceil(B / instances per launch) sequential launches.
+ * The plan is the smallest states per thread at which these stay within
+ * IRLMX_EXT_GRID_MAX_LAUNCHES (default 1: the measured break-even, DESIGN.md
+ * section 4 "Extended range"; 0 switches the shape off, as IRLMX_GRID=0
+ * does); at none, the call goes per sweep.  A launch whose workgroups
+ * cannot all run at once, or whose exchange times out, sends the whole call
+ * to the per-sweep shape (counters IRLMX_CTR_RERUN_*): same bits.  Per sweep:
+ * everything else, 2*S - 1 launches (correct, and slow at config-4 size).
  */
 int irlmx_backward_maxent_extended(const irlmx_mdp* mdp, const double* reward, const uint8_t* terminal,
                                    double* p_action, int32_t* status, void* workspace, size_t workspace_bytes,
@@ -433,7 +448,9 @@ int irlmx_value_iteration_numpy_order(const irlmx_mdp* mdp, const double* reward
                                       never takes the cluster shape (its overflow bookkeeping is per sweep) */
 #define IRLMX_PLAN_EXTENDED_RANGE 0x200 /* OR into op (IRLMX_OP_BACKWARD only, here and in irlmx_workspace_bytes):
                                           irlmx_backward_maxent_extended -- shape fused or sweep, [5], [7], [8]
-                                          (sweep: the 2*S - 1 sweep launches) and [9] */
+                                          (sweep: the 2*S - 1 sweep launches) and [9]; or grid: [2] 1 = each
+                                          instance on one XCD, [3] workgroups per instance, [4] instances per
+                                          launch, [5], [7] = 256, [8] sequential launches */
 int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* plan);
 
 /*

@@ -25,67 +25,22 @@
 // There is no rescaling, no per-sweep maximum and no convergence test; the
 // sweep count is the reference's 2*S (maxent.py:154), the last one per action.
 //
-// Two shapes: fused (one workgroup per instance, mantissas and exponents
-// ping-pong in LDS, 24 B per state, one barrier per sweep) and per sweep (one
-// launch per sweep over all instances, buffers in the caller's workspace; the
-// launch count is fixed, so the host never polls).
+// Three shapes: fused (one workgroup per instance, mantissas and exponents
+// ping-pong in LDS, 24 B per state, one barrier per sweep), the persistent grid
+// shape (extended_grid.hip: from 8,192 states on, one launch for all sweeps,
+// the pairs exchanged as tagged granules) and per sweep (one launch per sweep
+// over all instances, buffers in the caller's workspace; the launch count is
+// fixed, so the host never polls).
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <climits>
 
-#include "common.h"
-#include "fixed_point.h"
+#include "cluster.h"
+#include "extended.h"
+#include "grid.h"
 
 namespace irlmx {
-
-constexpr int kExtZero = INT_MIN;      // exponent of an exact zero: never raises a maximum
-constexpr int kExtMinShift = -1100;    // ldexp(m, shift) is 0 below -1075 already
-constexpr int kExtMaxStates = 1 << 19; // |e| grows by < 1100 per sweep: no int32 wrap within 2*S sweeps
-constexpr size_t kExtLdsPerState = 2 * sizeof(double) + 2 * sizeof(int);
-constexpr size_t kExtLdsMax = 160 * 1024;
-
-struct ExtArgs {
-  Model m;
-  const double* w;  // [B][K][S] collapsed, reward-folded weights (bwd_weights_kernel)
-  const double* reward;
-  const uint8_t* term;
-  const int32_t* bad;  // [B] non-finite weights (bwd_nonfinite_rule)
-  double* pi;          // [B][S][A]
-  int32_t* status;
-};
-
-struct ExtWs {
-  double* wgt;     // [B][K][S]
-  int32_t* bad;    // [B]
-  double* man[2];  // [B][S] mantissas, ping and pong (per-sweep shape)
-  int32_t* exp[2]; // [B][S] exponents
-  size_t total;
-};
-
-// m * 2^(e - E) with the shift clamped to [kExtMinShift, 0]: the difference is
-// taken in 64 bits (e and E may be far apart, or kExtZero).  A slot whose
-// weight is 0 may hold e > E; its product is 0 at any finite shift.
-__device__ inline double ext_aligned(double mant, int e, int E) {
-  const long long d = (long long)e - (long long)E;
-  const int sh = d < kExtMinShift ? kExtMinShift : (d > 0 ? 0 : (int)d);
-  return ldexp(mant, sh);
-}
-
-// acc -> (mantissa, exponent) on top of the alignment exponent E
-__device__ inline void ext_split(double acc, int E, double* mant, int* e) {
-  if (acc == 0.0) { *mant = 0.0; *e = kExtZero; return; }
-  if (!isfinite(acc)) { *mant = acc; *e = 0; return; }  // non-finite weights: the instance is NaN-filled
-  int d;
-  *mant = frexp(acc, &d);
-  *e = E + d;
-}
-
-__device__ inline void ext_init_state(bool terminal, double* mant, int* e) {
-  *mant = terminal ? 0.5 : 0.0;  // 1 = 0.5 * 2^1
-  *e = terminal ? 1 : kExtZero;
-}
 
 // The last sweep, per action (maxent.py:155-159): every action of a state is
 // aligned to the same E, za = er * acc rounded, the sequential action sum, and
@@ -287,7 +242,60 @@ static bool ext_fused_shape(const Model& m, FusedShape* out) {
   return ext_pair_ok(out->spt, out->kmax) && ext_fused_lds(m) <= kExtLdsMax;
 }
 
-static ExtWs ext_carve(const Model& m, void* base) {
+// Sequential launches above which a batch goes per sweep instead
+// (IRLMX_EXT_GRID_MAX_LAUNCHES; measured, DESIGN.md section 4 "Extended range").
+constexpr int kExtGridMaxLaunches = 1;
+// Fewest states of the grid shape (IRLMX_EXT_GRID_MIN_STATES): an absolute
+// count, twice the fused limit, whatever IRLMX_FUSED_MAX_STATES says.
+constexpr int kExtGridMinStates = 8192;
+
+// Workgroups per CU a launch without XCD grouping is planned for.  Measured
+// (DESIGN.md section 4 "Extended range"): four 256 x 256 instances at one state
+// per thread, 1,024 workgroups at 4 per CU with their hand-offs crossing XCDs,
+// ran 1,291 ms against 1,170 ms per sweep; at two states per thread, 512
+// workgroups at 2 per CU, 959 ms.  Grouped launches (every instance inside one
+// XCD's L2) keep the full capacity: 16 128 x 128 instances at 4 per CU, 4.0 us
+// per sweep.
+constexpr int kExtGridPerCuUngrouped = 2;
+
+// The persistent grid shape of the extended pass (after the fused shape,
+// before the per-sweep one): the smallest states-per-thread whose launches,
+// each with as many instances as fit, stay within the launch cap.  Each
+// instance within one XCD's share (grid_plan's rule, from 8 instances on) when
+// that costs no further launch.
+static bool ext_grid_plan(const Model& m, ExtGridPlan* out) {
+  if (m.dense || env_int("IRLMX_GRID", 1) == 0) return false;
+  if (m.S < env_int("IRLMX_EXT_GRID_MIN_STATES", kExtGridMinStates)) return false;
+  if (m.A > kMaxActions || 2LL * m.S + 1 > 0xFFFFFLL) return false;  // sweep tags: 20 bits
+  const int kmax = m.K <= 5 ? 5 : (m.K <= 8 ? 8 : (m.K <= 16 ? 16 : 0));
+  if (!kmax) return false;
+  const int max_launches = env_int("IRLMX_EXT_GRID_MAX_LAUNCHES", kExtGridMaxLaunches);
+  const int forced_cus = env_int("IRLMX_PLAN_CUS", 0);
+  const int cus = forced_cus > 0 ? forced_cus : device_cus();
+  for (int spt = 1; spt <= 4; spt *= 2) {
+    void* fn = ext_grid_fn(spt, kmax);
+    if (!fn) continue;
+    const int bpi = (m.S + spt * kGridThreads - 1) / (spt * kGridThreads);
+    if (bpi > kGridThreads) continue;  // the block words are gathered one per thread
+    const int cap = launch_capacity(fn, kGridThreads);
+    if (cap < bpi) continue;  // not even one instance is co-resident
+    // (one instance alone may take the whole capacity: there is nothing to split)
+    const int plain = std::min(m.B, std::max(1, std::min(cap, kExtGridPerCuUngrouped * cus) / bpi));
+    const int grouped = 8 * ((cap / 8) / bpi);
+    int ipl = plain, xcd = 0;
+    if (env_int("IRLMX_XCD_GROUP", 1) != 0 && m.B >= 8 && grouped >= 8) {
+      const int gi = std::min(m.B, grouped);
+      if ((m.B + gi - 1) / gi <= (m.B + plain - 1) / plain) { ipl = gi; xcd = 1; }
+    }
+    const int launches = (m.B + ipl - 1) / ipl;
+    if (launches > max_launches) continue;  // more states per thread: fewer workgroups per instance
+    *out = ExtGridPlan{spt, kmax, bpi, xcd, ipl, launches};
+    return true;
+  }
+  return false;
+}
+
+static ExtWs ext_carve(const Model& m, void* base, ExtGridWs* grid = nullptr) {
   ExtWs w;
   size_t off = 0;
   char* p = (char*)base;
@@ -303,6 +311,16 @@ static ExtWs ext_carve(const Model& m, void* base) {
   w.bad = (int32_t*)take(B * sizeof(int32_t));
   for (int i = 0; i < 2; ++i) w.man[i] = (double*)take(sweep ? B * S * sizeof(double) : 0);
   for (int i = 0; i < 2; ++i) w.exp[i] = (int32_t*)take(sweep ? B * S * sizeof(int32_t) : 0);
+  // grid shape: the granules of one launch's instances, beside the per-sweep
+  // buffers (which its rerun needs)
+  ExtGridPlan gp;
+  ExtGridWs g{nullptr, nullptr, nullptr};
+  if (sweep && ext_grid_plan(m, &gp)) {
+    g.gran = (unsigned long long*)take((size_t)gp.ipl * 6 * S * 16);
+    g.dgran = (unsigned long long*)take((size_t)gp.ipl * 4 * gp.bpi * 16);
+    g.err = (int*)take(4 * sizeof(int));
+  }
+  if (grid) *grid = g;
   w.total = off;
   return w;
 }
@@ -331,6 +349,17 @@ void extended_plan(const Model& m, int64_t* plan) {
     plan[9] = (int64_t)ext_fused_lds(m);
     return;
   }
+  ExtGridPlan gp;
+  if (ext_grid_plan(m, &gp)) {
+    plan[0] = IRLMX_SHAPE_GRID;
+    plan[2] = gp.xcd;
+    plan[3] = gp.bpi;
+    plan[4] = gp.ipl;
+    plan[5] = gp.spt;
+    plan[7] = kGridThreads;
+    plan[8] = gp.launches;
+    return;
+  }
   plan[0] = IRLMX_SHAPE_SWEEP;
   plan[5] = 1;
   plan[7] = kSweepThreads;
@@ -356,7 +385,8 @@ extern "C" int irlmx_backward_maxent_extended(const irlmx_mdp* mdp, const double
     return IRLMX_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  ExtWs ws = ext_carve(m, workspace);
+  ExtGridWs gws;
+  ExtWs ws = ext_carve(m, workspace, &gws);
   hipError_t e = hipMemsetAsync(ws.bad, 0, (size_t)m.B * sizeof(int32_t), st);
   if (e != hipSuccess) return hip_fail(e, "workspace memset");
   bwd_weights_launch(m, reward, ws.wgt, ws.bad, st);
@@ -371,6 +401,11 @@ extern "C" int irlmx_backward_maxent_extended(const irlmx_mdp* mdp, const double
     hipLaunchKernelGGL(kfn, dim3(m.B), dim3(fs.threads), lds, st, a);
     e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(e, "ext_fused_kernel");
+  }
+  ExtGridPlan gp;
+  if (gws.gran && ext_grid_plan(m, &gp)) {  // persistent launches; a rendezvous miss reruns the whole call below
+    const int rc = ext_grid_run(m, gp, a, gws, st);
+    if (rc != kClusterNotResident) return rc;
   }
   const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
   count_event(IRLMX_CTR_SWEEP_CALLS);

@@ -47,7 +47,11 @@ more than float64's exponent range (a reward contrast of 4 on a grid 256 wide)
 comes back with NaN rows and, beside them, finite rows that are wrong.
 ``True`` runs every backward with one exponent per state
 (``ops.backward_maxent_extended``); ``"auto"`` reruns only the instances that
-show the symptom.
+show the symptom.  From 8192 states on the extended pass runs the instances
+that can be co-resident in one persistent launch (and then synchronises the
+stream); a rerun set that would need more sequential launches than
+``IRLMX_EXT_GRID_MAX_LAUNCHES`` takes one launch per sweep, as every model
+between 4096 and 8192 states does.
 """
 
 import numpy as np

@@ -43,7 +43,9 @@ def execution_plan(mdp, op, rescale=True, extended_range=False):
     states per lane, in-tile layout, threads, sequential launches, LDS bytes.
     ``rescale=False``: the plan of ``backward_maxent(..., rescale=False)``.
     ``extended_range=True`` (``op="backward"`` only): the plan of
-    ``backward_maxent_extended`` -- "fused", or "sweep" with its 2*S - 1 launches."""
+    ``backward_maxent_extended`` -- "fused", "grid" (G: 1 = each instance on one
+    XCD, C workgroups per instance, instances per launch, sequential launches)
+    or "sweep" with its 2*S - 1 launches."""
     import ctypes
     lib = _lib.load()
     buf = (ctypes.c_int64 * len(PLAN_FIELDS))()
@@ -116,8 +118,14 @@ def backward_maxent_extended(mdp, reward, terminal):
     partition vector spans more than float64's exponent range and
     ``backward_maxent`` returns NaN rows and wrong finite rows beside them;
     bit-identical to ``backward_maxent`` where that pass stays in range.
-    STENCIL5 and ELL models.  Above 4096 states it runs one launch per sweep
-    (2*S - 1 launches: slow at config-4 size)."""
+    STENCIL5 and ELL models.  Up to 4096 states one workgroup per instance;
+    from 8192 states on (at most 16 slots per state, 2^18 states) one persistent
+    launch for all sweeps of the instances that can be co-resident -- the call
+    then synchronises the stream; whatever is in between, larger, or a batch
+    that would need more sequential launches than
+    ``IRLMX_EXT_GRID_MAX_LAUNCHES`` runs one launch per sweep (2*S - 1
+    launches: slow at config-4 size).  ``execution_plan(...,
+    extended_range=True)`` names the shape."""
     lib = _lib.load()
     B, S, A = mdp.batch, mdp.n_states, mdp.n_actions
     r = _f64(reward, mdp, (B, S))

@@ -32,6 +32,9 @@ Deliberate differences (documented in DESIGN.md):
   rescaled pass keeps one scale per instance: NaN rows, and wrong finite rows
   beside them).  The numpy-order attempt and ``IRLMX_REFERENCE_OVERFLOW=1``
   keep precedence; unset, nothing changes.  DENSE tables are not covered.
+  One workgroup up to 4096 states, one persistent launch from 8192 states on
+  (a 256 x 256 grid: 131,072 sweeps in one launch), one launch per sweep in
+  between (``ops.backward_maxent_extended``).
 """
 
 import os

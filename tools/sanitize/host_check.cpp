@@ -18,7 +18,8 @@
 //  * every argument-validation path of every entry point (null models, bad
 //    sizes, unknown layouts, NULL arrays, short workspaces), with the error text;
 //  * the extended-range backward (extended.hip): its plan and workspace
-//    (IRLMX_PLAN_EXTENDED_RANGE) for every stencil and ELL model above, the
+//    (IRLMX_PLAN_EXTENDED_RANGE) for every stencil and ELL model above --
+//    fused, the persistent grid shape (extended_grid.hip) or per sweep --, the
 //    flag's refusal on the other ops and on DENSE tables, and the validation
 //    and workspace paths of irlmx_backward_maxent_extended;
 //  * policy evaluation (policy_eval.hip): the plan and workspace of
@@ -172,9 +173,32 @@ static void extended_plan_and_workspace(const irlmx_mdp& m, const char* what) {
   const size_t S = (size_t)m.n_states, B = (size_t)m.batch;
   const size_t K = m.layout == IRLMX_LAYOUT_STENCIL5 ? 5 : (size_t)m.k_row;
   size_t floor = B * K * S * sizeof(double) + B * sizeof(int32_t);
-  CHECK(p[0] == IRLMX_SHAPE_FUSED || p[0] == IRLMX_SHAPE_SWEEP, "%s: extended shape %lld", what, (long long)p[0]);
-  CHECK(p[1] == 0 && p[2] == 0 && p[3] == 0 && p[4] == 0 && p[6] == 0, "%s: extended plan cluster fields", what);
-  if (p[0] == IRLMX_SHAPE_FUSED) {
+  CHECK(p[0] == IRLMX_SHAPE_FUSED || p[0] == IRLMX_SHAPE_SWEEP || p[0] == IRLMX_SHAPE_GRID, "%s: extended shape %lld",
+        what, (long long)p[0]);
+  CHECK(p[1] == 0 && p[6] == 0, "%s: extended plan cluster fields", what);
+  CHECK(p[0] == IRLMX_SHAPE_GRID || (p[2] == 0 && p[3] == 0 && p[4] == 0), "%s: extended plan grid fields", what);
+  size_t slack = 8 * 256;
+  if (p[0] == IRLMX_SHAPE_GRID) {
+    // the persistent grid shape (extended_grid.hip): from 8,192 states on, up to 16 slots, workgroups of 256
+    // threads, [3] of them per instance, [4] instances per launch within the planned capacity, [8] launches
+    ++g_ext_shapes[1];
+    const int64_t xcd = p[2], bpi = p[3], ipl = p[4], spt = p[5], nl = p[8];
+    CHECK(S >= 8192 && S <= (size_t(1) << 18) && K <= 16, "%s: extended grid at S %zu K %zu", what, S, K);
+    CHECK(((spt == 1 && K <= 16) || (spt == 2 && K <= 8) || (spt == 4 && K <= 5)) && p[7] == 256 && p[9] == 0, "%s: extended grid spt %lld",
+          what, (long long)spt);
+    CHECK(bpi == ((int64_t)S + 256 * spt - 1) / (256 * spt) && bpi <= 256, "%s: extended grid bpi %lld", what,
+          (long long)bpi);
+    CHECK(ipl >= 1 && ipl <= (int64_t)B && ipl * bpi <= 4 * kCus, "%s: extended grid %lld instances x %lld", what,
+          (long long)ipl, (long long)bpi);
+    CHECK(xcd == 0 || (xcd == 1 && B >= 8 && (ipl + 7) / 8 * bpi <= 4 * kCus / 8), "%s: extended grid xcd %lld", what,
+          (long long)xcd);
+    CHECK(xcd == 1 || ipl == 1 || ipl * bpi <= 2 * kCus, "%s: extended grid, ungrouped: %lld instances x %lld", what,
+          (long long)ipl, (long long)bpi);
+    CHECK(nl == ((int64_t)B + ipl - 1) / ipl && nl >= 1, "%s: extended grid launches %lld", what, (long long)nl);
+    // the per-sweep buffers (the rerun's), one launch's granules and block words, the err words
+    floor += B * S * 2 * (sizeof(double) + sizeof(int32_t)) + (size_t)ipl * (96 * S + 64 * (size_t)bpi) + 16;
+    slack += 3 * 256;
+  } else if (p[0] == IRLMX_SHAPE_FUSED) {
     ++g_ext_shapes[0];
     CHECK(S <= 4096 && K <= 32, "%s: extended fused at S %zu K %zu", what, S, K);
     CHECK(p[7] >= 64 && p[7] <= 1024 && p[7] % 64 == 0, "%s: extended fused threads %lld", what, (long long)p[7]);
@@ -186,7 +210,7 @@ static void extended_plan_and_workspace(const irlmx_mdp& m, const char* what) {
     CHECK(p[5] == 1 && p[7] == 256 && p[8] == 2 * (int64_t)S - 1 && p[9] == 0, "%s: extended sweep plan", what);
     floor += B * S * 2 * (sizeof(double) + sizeof(int32_t));
   }
-  CHECK(ws >= floor && ws <= floor + 8 * 256 && ws % 256 == 0, "%s: extended workspace %zu (floor %zu)", what, ws, floor);
+  CHECK(ws >= floor && ws <= floor + slack && ws % 256 == 0, "%s: extended workspace %zu (floor %zu)", what, ws, floor);
   for (int other = IRLMX_OP_FORWARD; other <= IRLMX_OP_VALUE_ITERATION; ++other) {
     CHECK(irlmx_execution_plan(&m, other | IRLMX_PLAN_EXTENDED_RANGE, p) == IRLMX_EINVAL &&
               strstr(irlmx_last_error(), "IRLMX_OP_BACKWARD only"),
@@ -549,7 +573,8 @@ static void dump_plans() {
                                      {"IRLMX_FUSED_MAX_STATES", "0"},
                                      {"IRLMX_CLUSTER", "0"},
                                      {"IRLMX_GRID", "0"},
-                                     {"IRLMX_DENSE_GEMM_MIN", "1"}};
+                                     {"IRLMX_DENSE_GEMM_MIN", "1"},
+                                     {"IRLMX_EXT_GRID_MAX_LAUNCHES", "1000"}};
   const int ops[] = {IRLMX_OP_BACKWARD, IRLMX_OP_FORWARD, IRLMX_OP_SOFT_BACKWARD, IRLMX_OP_VALUE_ITERATION,
                      IRLMX_OP_BACKWARD | IRLMX_PLAN_NO_RESCALE, IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE,
                      IRLMX_OP_POLICY_EVALUATION};
@@ -596,8 +621,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
     return 1;
   }
-  CHECK(g_ext_shapes[0] > 100 && g_ext_shapes[2] > 100, "extended shapes planned: fused %lld sweep %lld",
-        g_ext_shapes[0], g_ext_shapes[2]);
+  CHECK(g_ext_shapes[0] > 100 && g_ext_shapes[1] > 100 && g_ext_shapes[2] > 100,
+        "extended shapes planned: fused %lld grid %lld sweep %lld", g_ext_shapes[0], g_ext_shapes[1], g_ext_shapes[2]);
   if (g_fail) {
     fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
     return 1;
