@@ -58,6 +58,8 @@ extern "C" {
 #define IRLMX_OP_SOFT_BACKWARD 3
 #define IRLMX_OP_VALUE_ITERATION 4
 #define IRLMX_OP_POLICY_EVALUATION 6 /* 5 stays an unknown op: ABI version 1 has always answered "unknown op 5" */
+#define IRLMX_OP_BACKWARD_HORIZON 8  /* 5 and 7 stay unknown ops: tests and tools/sanitize pin both answers */
+#define IRLMX_OP_FORWARD_HORIZON 9
 
 /*
  * Transition model P[from, to, action] of B instances (the reference's dense
@@ -317,6 +319,78 @@ int irlmx_policy_evaluation(const irlmx_mdp* mdp, const double* reward, const do
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Finite-horizon MaxEnt (no reference counterpart: the reference's passes,
+ * maxent.py:63-159, are episodic): Ziebart's Algorithm 1 for a fixed number
+ * of steps T = `horizon`, for models without a terminal state and for
+ * demonstrations cut after T steps (irlmx_rollout's IRLMX_TRAJ_TRUNCATED).  A
+ * visited state contributes its reward, the final one included (as `visits`
+ * counts the final state), so with er = exp(reward), a path s_0 .. s_T has
+ * weight prod_t er(s_t) P(s_t -> s_t+1 | a_t).
+ *
+ * irlmx_backward_maxent_horizon, for t = T-1 .. 0 from Z_T(s) = er(s):
+ *   za_t(s,a) = er(s) * sum_k P[s, target_k(s), a] * Z_{t+1}(target_k(s))
+ *   Z_t(s)    = sum_a za_t(s,a)       (terminal s: Z_t(s) = er(s), held: absorbing)
+ *   pi_t(s,a) = za_t(s,a) / Z_t'(s)   Z_t' = the sum just formed, also at terminal states
+ * Every Z is held as m * 2^e (m a float64 in [0.5, 1) or 0, e an int32, an
+ * exact zero apart: irlmx_backward_maxent_extended's form).  Per state and
+ * step the statement order is:
+ *   1. E = the largest neighbour exponent over the slots where some action has
+ *      a nonzero entry.
+ *   2. Per action, acc = fma(P, aligned z, acc) in slot order, then za = er * acc
+ *      rounded (aligned z = m * 2^(e - E), the shift clamped to [-1100, 0]).
+ *   3. zsum = the sequential action sum.
+ *   4. pi = za / zsum.
+ *   5. (m, d) = frexp(zsum), e = E + d gives Z_t(s).
+ * An instance with non-finite exp(r) writes NaN to every row of every step
+ * (and to log_z0), and status stays IRLMX_OK, as the extended backward does;
+ * 0 / 0 = NaN where no successor has weight.
+ *   reward [B][S]; terminal [B][S] or NULL (no terminal state)
+ *   horizon    1 .. 2^20, IRLMX_EINVAL outside: the exponent grows by less
+ *              than 1,100 per step, so there is no int32 wrap
+ *   p_action_t [B][T][S][A] out: pi_t, B * T * S * A * 8 bytes
+ *   log_z0     [B][S] out or NULL: log Z_0(s) = fma((double)e, ln 2, log(m)),
+ *              -inf for an exact zero: the log partition function of the paths
+ *              from s (in a deterministic world sum_t r(s_t) - log Z_0(s_0) is
+ *              a demonstration's exact log-likelihood)
+ *
+ * irlmx_forward_svf_horizon, for t = 0 .. T-1 from d_0 = p0 and D = p0:
+ *   w           = sum_a fma(P[u -> s', a], pi_t[u][a], w)   action order from 0; 0 for terminal u
+ *   d_{t+1}(s') = sum_k fma(w_k, d_t[u_k], acc)             slot order of the column form (every
+ *                 slot: an off-grid STENCIL5 slot has w = 0 and u_k = s'; ELL slots as stored)
+ *   D(s')       = D(s') + d_{t+1}(s')                       one rounded add per step
+ *   svf [B][S] out = D; svf_t [B][T+1][S] out or NULL: the marginals d_0 .. d_T
+ * status: IRLMX_NONFINITE if and only if the instance's returned svf holds a
+ * non-finite entry; NaN propagates by IEEE rules in the order above (there is
+ * no whole-instance poisoning rule and no convergence test).  The sweep count
+ * is T.  Without terminals sum_s d_t(s) = 1 for every t, so sum D = T + 1.
+ * In float64 (u = 2^-53, K_c column slots): a step rounds A times per weight
+ * and K_c times per sum, so d_t is off by at most t (K_c + A) u relatively and
+ * so is sum_s d_t, a sum of non-negative terms; D takes at most T rounded adds
+ * of non-negative terms, T u more.  To first order every one of the T + 1
+ * marginals in D is off by less than (T + 1) (K_c + A + 2) u relatively, and
+ * with them |sum D - (T + 1)| / (T + 1) <= (T + 1) (K_c + A + 2) 2^-53: the
+ * worst case.
+ *
+ * Both: STENCIL5 and ELL layouts, IRLMX_EINVAL for DENSE.  Two shapes, the
+ * same bits in both: models of at most 1024 states whose slots fit the fused
+ * planner (irlmx_execution_plan) run one workgroup per instance for all T
+ * steps, and so do models of up to 4096 states once the batch holds a
+ * workgroup for every CU (IRLMX_HORIZON_FUSED_BATCH moves that count: below
+ * it one launch per step is faster, DESIGN.md section 4 "Finite horizon");
+ * everything else one launch per step.  Both are fully asynchronous on
+ * `stream`.  Workspace: irlmx_workspace_bytes(mdp, IRLMX_OP_BACKWARD_HORIZON /
+ * IRLMX_OP_FORWARD_HORIZON), independent of T.
+ */
+int irlmx_backward_maxent_horizon(const irlmx_mdp* mdp, const double* reward, const uint8_t* terminal /* may be NULL */,
+                                  int32_t horizon, double* p_action_t /* [B][T][S][A] */,
+                                  double* log_z0 /* [B][S], may be NULL */, int32_t* status, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int irlmx_forward_svf_horizon(const irlmx_mdp* mdp, const double* p_initial, const uint8_t* terminal /* may be NULL */,
+                              const double* p_action_t, int32_t horizon, double* svf /* [B][S] */,
+                              double* svf_t /* [B][T+1][S], may be NULL */, int32_t* status, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
+/*
  * Demonstrations on the device (no reference counterpart beyond the statistics
  * of maxent.py:15-60: the reference samples with numpy's global generator,
  * trajectory.py:52-128, which the trajectory.py drop-in follows draw for draw).
@@ -430,6 +504,9 @@ int irlmx_value_iteration_numpy_order(const irlmx_mdp* mdp, const double* reward
  * IRLMX_OP_POLICY_EVALUATION plans the fused shape ([5], [7], [8] = 1, [9]) or
  * the per-sweep one ([5] = 1, [7]; [8] = 0: its launch count is the sweep
  * count); IRLMX_EINVAL for DENSE, here and 0 from irlmx_workspace_bytes.
+ * IRLMX_OP_BACKWARD_HORIZON / IRLMX_OP_FORWARD_HORIZON likewise: fused ([5],
+ * [7], [8] = 1, [9]) or per sweep ([5] = 1, [7]; [8] = 0: its launch count is
+ * the horizon); IRLMX_EINVAL for DENSE.
  * A backward plan assumes rescale != 0 unless op carries IRLMX_PLAN_NO_RESCALE.
  */
 #define IRLMX_PLAN_LEN 10

@@ -1,8 +1,8 @@
 // Model views, the workspace, the stopping-rule helpers, the argument struct
 // of the Bellman kernels and the host helpers of the fixed-point passes that
 // more than one translation unit uses (fixed_point.hip defines the host
-// functions; grid.hip, numpy_order.hip, extended.hip and policy_eval.hip are
-// the other users).
+// functions; grid.hip, numpy_order.hip, extended.hip, policy_eval.hip and
+// horizon.hip are the other users).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -333,5 +333,13 @@ void extended_plan(const Model& m, int64_t* plan);
 // Policy evaluation (policy_eval.hip): whether this model is one it runs (else
 // IRLMX_EINVAL and the message, prefixed by `fn`).
 int policy_eval_check_model(const Model& m, const char* fn);
+
+// The finite-horizon passes (horizon.hip; op IRLMX_OP_BACKWARD_HORIZON or
+// IRLMX_OP_FORWARD_HORIZON): whether this model is one they run (else
+// IRLMX_EINVAL and the message, prefixed by `fn`), their workspace and plan.
+inline bool horizon_op(int op) { return op == IRLMX_OP_BACKWARD_HORIZON || op == IRLMX_OP_FORWARD_HORIZON; }
+int horizon_check_model(const Model& m, const char* fn);
+size_t horizon_workspace_bytes(const Model& m, int op);
+void horizon_plan(const Model& m, int op, int64_t* plan);
 
 }  // namespace irlmx

@@ -1000,6 +1000,7 @@ extern "C" size_t irlmx_workspace_bytes(const irlmx_mdp* mdp, int32_t op) {
   const Model m = make_model(mdp);
   if (extended_op(op)) return check_extended_op(m, op, "workspace_bytes") ? 0 : extended_workspace_bytes(m);
   if (op == IRLMX_OP_POLICY_EVALUATION && policy_eval_check_model(m, "workspace_bytes")) return 0;
+  if (horizon_op(op)) return horizon_check_model(m, "workspace_bytes") ? 0 : horizon_workspace_bytes(m, op);
   return carve(m, op, nullptr).total;
 }
 
@@ -1016,8 +1017,9 @@ extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* p
   // (a backward call with rescale = 0 never takes the cluster shape: see irlmx_backward_maxent)
   const bool no_rescale = op > 0 && (op & IRLMX_PLAN_NO_RESCALE) != 0;
   if (no_rescale) op &= ~IRLMX_PLAN_NO_RESCALE;
-  // (IRLMX_OP_POLICY_EVALUATION is 6: the value between stays the unknown op it has always been)
-  if (op < IRLMX_OP_BACKWARD || (op > IRLMX_OP_VALUE_ITERATION && op != IRLMX_OP_POLICY_EVALUATION)) {
+  // (IRLMX_OP_POLICY_EVALUATION is 6 and the horizon ops 8 and 9: the values between stay the unknown
+  // ops they have always been)
+  if (op < IRLMX_OP_BACKWARD || (op > IRLMX_OP_VALUE_ITERATION && op != IRLMX_OP_POLICY_EVALUATION && !horizon_op(op))) {
     set_error("unknown op %d", op);
     return IRLMX_EINVAL;
   }
@@ -1026,6 +1028,11 @@ extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* p
   if (op == IRLMX_OP_POLICY_EVALUATION)
     if (int rc = policy_eval_check_model(m, "execution_plan")) return rc;
   for (int i = 0; i < IRLMX_PLAN_LEN; ++i) plan[i] = 0;
+  if (horizon_op(op)) {
+    if (int rc = horizon_check_model(m, "execution_plan")) return rc;
+    horizon_plan(m, op, plan);
+    return 0;
+  }
   // (the compact layout is data-dependent: from the table's properties, else checked on the device)
   const Route r = route(m, op, !no_rescale, [&] { return bwd_compact(m, nullptr, nullptr); });
   plan[0] = r.shape;

@@ -1,0 +1,642 @@
+// Finite-horizon MaxEnt (irlmx_backward_maxent_horizon, irlmx_forward_svf_horizon)
+// on gfx950: Ziebart's Algorithm 1 for a fixed number of steps T, with no
+// terminal state needed.
+//
+// Backward, for t = T-1 .. 0 from Z_T(s) = er(s) = exp(r(s)):
+//
+//   za_t(s,a) = er(s) * sum_k P[s, target_k(s), a] * Z_{t+1}(target_k(s))
+//   Z_t(s)    = sum_a za_t(s,a)      (terminal s: Z_t(s) = er(s), held)
+//   pi_t(s,a) = za_t(s,a) / Z_t'(s)  (Z_t' the sum just formed, also at terminals)
+//
+// Every Z is m * 2^e (extended.h); a step is "the last sweep, per action" of
+// the extended backward (ext_policy_row's statement order) done at every step:
+//   1. E = the largest neighbour exponent over the slots where some action has
+//      a nonzero entry
+//   2. per action, acc = fma(P, aligned z, acc) in slot order, za = er * acc rounded
+//   3. zsum = the sequential action sum
+//   4. pi = za / zsum
+//   5. ext_split(zsum, E) gives Z_t(s)
+//
+// Forward, for t = 0 .. T-1 from d_0 = p0, D = p0:
+//
+//   w           = sum_a fma(P[u -> s', a], pi_t[u][a], w)   action order from 0; 0 for terminal u
+//   d_{t+1}(s') = sum_k fma(w_k, d_t[u_k], acc)             every slot of the column form in slot
+//                                                           order (fwd_weights_kernel's access: an
+//                                                           off-grid stencil slot has w = 0, u = s')
+//   D(s')       = D(s') + d_{t+1}(s')                       one rounded add per step
+//
+// Two shapes per pass, chosen like policy evaluation's: fused -- one workgroup
+// per instance for all T steps, (mantissa, exponent) pairs (backward) or d_t
+// (forward) ping-pong in LDS, one barrier per step -- and per sweep: one launch
+// per step over all instances, buffers in the caller's workspace; the launch
+// count is T, so the host never polls.  Same statements in both: the same bits.
+// There is no persistent multi-CU shape ("Finite horizon").
+
+#include <hip/hip_runtime.h>
+
+#include "extended.h"
+#include "fixed_point.h"
+
+namespace irlmx {
+
+constexpr int kHzMaxHorizon = 1 << 20;  // |e| grows by < 1100 per step: no int32 wrap
+constexpr int kHzRegActions = 4;        // actions of the register-resident table variant
+
+struct HzBwdArgs {
+  Model m;
+  const double* reward;
+  const uint8_t* term;  // may be null
+  int T;
+  double* pi;      // [B][T][S][A]
+  double* log_z0;  // [B][S], may be null
+  int32_t* status;
+};
+
+struct HzFwdArgs {
+  Model m;
+  const double* p0;
+  const uint8_t* term;  // may be null
+  const double* pi;     // [B][T][S][A]
+  int T;
+  double* svf;    // [B][S]
+  double* svf_t;  // [B][T+1][S], may be null
+  int32_t* status;
+};
+
+// per-sweep buffers (the fused kernels keep all of this in LDS)
+struct HzWs {
+  int32_t* bad;     // [B] backward: some exp(r) is non-finite
+  double* man[2];   // [B][S] backward mantissas / forward d_t, ping and pong
+  int32_t* exp[2];  // [B][S] backward exponents
+  size_t total;
+};
+
+__device__ inline size_t hz_pi_row(const Model& m, int T, int b, int t, int s) {
+  return (((size_t)b * T + t) * m.S + s) * m.A;
+}
+
+// log Z = e * ln 2 + log m; -inf for an exact zero
+__device__ inline double hz_log_z(double mant, int e) {
+  if (e == kExtZero) return -(double)INFINITY;
+  return fma((double)e, 0x1.62e42fefa39efp-1, log(mant));
+}
+
+// bwd_nonfinite_rule for this pass: a non-finite exp(r) anywhere in the instance
+__device__ inline void hz_nan_state(const HzBwdArgs& a, int b, int t, int s) {
+  double* out = a.pi + hz_pi_row(a.m, a.T, b, t, s);
+  for (int act = 0; act < a.m.A; ++act) out[act] = kNaN;
+  if (t == 0 && a.log_z0) a.log_z0[(size_t)b * a.m.S + s] = kNaN;
+}
+
+// One state of one backward step with its slot class compiled in (nbr(k) is
+// target_k(s), tab(act, k) is P[s, target_k(s), act]).  UNROLL: the action
+// loop is unrolled, which a table held in registers needs (constant indices).
+// A table read from memory keeps it rolled, so that only one action's loads
+// are in flight (unrolled, the compiler hoists all A * K of them and spills),
+// and za rests in the output row between the sum and the division (a dynamic
+// index into registers would go to scratch).  From 16 slots on the slot loop
+// is rolled too and nothing per slot is held.  Returns zsum, *Eout its
+// alignment exponent.
+template <int AMAX, int KMAX, bool UNROLL, class Nbr, class Tab>
+__device__ __attribute__((always_inline)) inline double hz_row(int K, int A, double er, const double* zm,
+                                                               const int* ze, Nbr&& nbr, unsigned any, Tab&& tab,
+                                                               double* out, int* Eout) {
+  int E = kExtZero;
+  constexpr bool kHold = KMAX <= 8;  // neighbours read once, aligned once; else LDS is read per action
+  double z[kHold ? KMAX : 1];
+  if constexpr (kHold) {
+    int e[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) {
+        e[k] = ze[nbr(k)];
+        if ((any >> k) & 1u) E = max(E, e[k]);
+      }
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) z[k] = k < K ? ext_aligned(zm[nbr(k)], e[k], E) : 0.0;
+  } else {
+#pragma unroll 4
+    for (int k = 0; k < K; ++k)
+      if ((any >> k) & 1u) E = max(E, ze[nbr(k)]);
+  }
+  auto action = [&](int act) __attribute__((always_inline)) {
+    double acc = 0.0;
+    if constexpr (kHold) {
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K) acc = fma(tab(act, k), z[k], acc);
+    } else {  // rolled: unrolled, 16 or 32 slots of loads in flight spill
+#pragma unroll 4
+      for (int k = 0; k < K; ++k) {
+        const int n = nbr(k);
+        acc = fma(tab(act, k), ext_aligned(zm[n], ze[n], E), acc);
+      }
+    }
+    return __dmul_rn(er, acc);
+  };
+  double zsum = 0.0;
+  if constexpr (UNROLL) {
+    double za[AMAX];
+#pragma unroll
+    for (int act = 0; act < AMAX; ++act)
+      if (act < A) {
+        za[act] = action(act);
+        zsum = __dadd_rn(zsum, za[act]);
+      }
+#pragma unroll
+    for (int act = 0; act < AMAX; ++act)
+      if (act < A) out[act] = za[act] / zsum;
+  } else {
+#pragma unroll 1
+    for (int act = 0; act < A; ++act) {
+      const double za = action(act);
+      out[act] = za;
+      zsum = __dadd_rn(zsum, za);
+    }
+#pragma unroll 1
+    for (int act = 0; act < A; ++act) out[act] = out[act] / zsum;
+  }
+  *Eout = E;
+  return zsum;
+}
+
+// The same statements with run-time loops (per-sweep shape: any K).
+__device__ inline double hz_row_loop(const Model& m, int b, int s, double er, const double* zm, const int* ze,
+                                     double* out, int* Eout) {
+  const int K = m.K, A = m.A;
+  int E = kExtZero;
+  for (int k = 0; k < K; ++k) {
+    bool any = false;
+    for (int act = 0; act < A; ++act) any |= row_val(m, b, act, k, s) != 0.0;
+    if (any) E = max(E, ze[row_nbr(m, b, s, k)]);
+  }
+  double za[kMaxActions];
+  double zsum = 0.0;
+  for (int act = 0; act < A; ++act) {
+    double acc = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const int n = row_nbr(m, b, s, k);
+      acc = fma(row_val(m, b, act, k, s), ext_aligned(zm[n], ze[n], E), acc);
+    }
+    za[act] = __dmul_rn(er, acc);
+    zsum = __dadd_rn(zsum, za[act]);
+  }
+  for (int act = 0; act < A; ++act) out[act] = za[act] / zsum;
+  *Eout = E;
+  return zsum;
+}
+
+// Folded forward weight of slot k of target t under pi_t (`pit`: the step's
+// [S][A] rows of instance b) and its source state: fwd_weights_kernel's access.
+__device__ inline double hz_fwd_weight(const Model& m, int b, int t, int k, const double* __restrict__ pit,
+                                       const uint8_t* __restrict__ tb, int* src) {
+  const int S = m.S, A = m.A;
+  double acc = 0.0;
+  if (m.stencil) {
+    const int s = stencil_nbr(t, k, m.W, m.H);
+    *src = s;
+    if (stencil_valid(t, k, m.W, m.H) && !(tb && tb[s])) {
+      const int kk = stencil_opposite(k);  // direction from s back to t
+      for (int a = 0; a < A; ++a) acc = fma(row_val(m, b, a, kk, s), pit[(size_t)s * A + a], acc);
+    }
+  } else {
+    const int s = col_src(m, b, t, k);
+    *src = s;
+    if (!(tb && tb[s])) {
+      const size_t base = inst_of(m, b) * A;
+      for (int a = 0; a < A; ++a) acc = fma(m.col_val[((base + a) * m.Kc + k) * S + t], pit[(size_t)s * A + a], acc);
+    }
+  }
+  return acc;
+}
+
+__device__ inline double hz_fwd_state(const Model& m, int b, int t, const double* __restrict__ pit,
+                                      const uint8_t* __restrict__ tb, const double* din) {
+  double acc = 0.0;
+  for (int k = 0; k < m.Kc; ++k) {
+    int u;
+    const double w = hz_fwd_weight(m, b, t, k, pit, tb, &u);
+    acc = fma(w, din[u], acc);
+  }
+  return acc;
+}
+
+// ---------------------------------------------------------------------------
+// fused shape: one workgroup per instance for all T steps
+// ---------------------------------------------------------------------------
+
+// REG: the A * K table values of every state of this lane stay in registers
+// (A <= kHzRegActions); otherwise they are read from memory each step (L2).
+template <int SPT, int KMAX, bool REG>
+__global__ void __launch_bounds__(1024) hz_bwd_fused_kernel(HzBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hz_smem[];
+  const Model& m = a.m;
+  const int S = m.S, K = m.K, A = m.A, T = a.T;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  double* manA = (double*)hz_smem;
+  double* manB = manA + S;
+  int* expA = (int*)(manB + S);
+  int* expB = expA + S;
+
+  constexpr bool kHoldNb = KMAX <= 8;  // from 16 slots on: row_nbr at every use (hz_row rolls its slot loop)
+  double er[SPT];
+  int nb[kHoldNb ? SPT : 1][kHoldNb ? KMAX : 1];
+  unsigned any[SPT];
+  bool term[SPT];
+  double tab[REG ? SPT : 1][REG ? kHzRegActions : 1][REG ? KMAX : 1];
+  int nonfinite = 0;
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    const int s = tid + j * nt;
+    er[j] = 1.0;
+    any[j] = 0u;
+    term[j] = false;
+    if constexpr (kHoldNb) {
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) nb[j][k] = 0;
+    }
+    if (s < S) {
+      er[j] = exp(a.reward[(size_t)b * S + s]);
+      nonfinite |= !isfinite(er[j]);
+      term[j] = a.term && a.term[(size_t)b * S + s] != 0;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K) {
+          if constexpr (kHoldNb) nb[j][k] = row_nbr(m, b, s, k);
+          bool nz = false;
+          for (int act = 0; act < A; ++act) nz |= row_val(m, b, act, k, s) != 0.0;
+          any[j] |= (nz ? 1u : 0u) << k;
+        }
+      if constexpr (REG) {
+#pragma unroll
+        for (int act = 0; act < kHzRegActions; ++act)
+#pragma unroll
+          for (int k = 0; k < KMAX; ++k) tab[j][act][k] = (act < A && k < K) ? row_val(m, b, act, k, s) : 0.0;
+      }
+      ext_split(er[j], 0, &manA[s], &expA[s]);  // Z_T = exp(r)
+    }
+  }
+  if (__syncthreads_or(nonfinite)) {  // NaN at every step (uniform over the workgroup)
+    for (int t = 0; t < T; ++t)
+      for (int s = tid; s < S; s += nt) hz_nan_state(a, b, t, s);
+    if (tid == 0) a.status[b] = IRLMX_OK;
+    return;
+  }
+
+  for (int it = 0; it < T; ++it) {
+    const int t = T - 1 - it;
+    const double* min_ = (it & 1) ? manB : manA;
+    const int* ein = (it & 1) ? expB : expA;
+    double* mout = (it & 1) ? manA : manB;
+    int* eout = (it & 1) ? expA : expB;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      const int s = tid + j * nt;
+      if (s < S) {
+        double* out = a.pi + hz_pi_row(m, T, b, t, s);
+        int E;
+        double zsum;
+        auto nbr = [&](int k) __attribute__((always_inline)) {
+          if constexpr (kHoldNb) return nb[j][k];
+          else return row_nbr(m, b, s, k);
+        };
+        if constexpr (REG)
+          zsum = hz_row<kHzRegActions, KMAX, true>(K, A, er[j], min_, ein, nbr, any[j],
+                                                   [&](int act, int k) { return tab[j][act][k]; }, out, &E);
+        else
+          zsum = hz_row<kMaxActions, KMAX, false>(K, A, er[j], min_, ein, nbr, any[j],
+                                                  [&](int act, int k) { return row_val(m, b, act, k, s); }, out, &E);
+        double zm;
+        int ze;
+        if (term[j]) ext_split(er[j], 0, &zm, &ze);  // absorbing: Z_t = exp(r), held
+        else ext_split(zsum, E, &zm, &ze);
+        mout[s] = zm;
+        eout[s] = ze;
+        if (t == 0 && a.log_z0) a.log_z0[(size_t)b * S + s] = hz_log_z(zm, ze);
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) a.status[b] = IRLMX_OK;
+}
+
+// d_t ping-pongs in LDS, D in registers; the weights are folded from pi_t
+// every step (nothing is held between steps but D)
+template <int SPT>
+__global__ void __launch_bounds__(1024) hz_fwd_fused_kernel(HzFwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hz_smem[];
+  const Model& m = a.m;
+  const int S = m.S, T = a.T;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  double* dA = (double*)hz_smem;
+  double* dB = dA + S;
+  const uint8_t* tb = a.term ? a.term + (size_t)b * S : nullptr;
+  double* marg = a.svf_t ? a.svf_t + (size_t)b * (T + 1) * S : nullptr;
+
+  double D[SPT];
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    const int s = tid + j * nt;
+    D[j] = 0.0;
+    if (s < S) {
+      D[j] = a.p0[(size_t)b * S + s];
+      dA[s] = D[j];
+      if (marg) marg[s] = D[j];
+    }
+  }
+  __syncthreads();
+  for (int t = 0; t < T; ++t) {
+    const double* din = (t & 1) ? dB : dA;
+    double* dout = (t & 1) ? dA : dB;
+    const double* pit = a.pi + hz_pi_row(m, T, b, t, 0);
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      const int s = tid + j * nt;
+      if (s < S) {
+        const double nd = hz_fwd_state(m, b, s, pit, tb, din);
+        dout[s] = nd;
+        D[j] = __dadd_rn(D[j], nd);
+        if (marg) marg[(size_t)(t + 1) * S + s] = nd;
+      }
+    }
+    __syncthreads();
+  }
+  int nonfinite = 0;
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    const int s = tid + j * nt;
+    if (s < S) {
+      a.svf[(size_t)b * S + s] = D[j];
+      nonfinite |= !isfinite(D[j]);
+    }
+  }
+  nonfinite = __syncthreads_or(nonfinite);
+  if (tid == 0) a.status[b] = nonfinite ? IRLMX_NONFINITE : IRLMX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// per-sweep shape: one launch per step over all instances
+// ---------------------------------------------------------------------------
+
+__global__ void hz_bwd_init_kernel(HzBwdArgs a, HzWs ws) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  if (s >= a.m.S) return;
+  const size_t i = (size_t)b * a.m.S + s;
+  const double er = exp(a.reward[i]);
+  if (!isfinite(er)) atomicOr(&ws.bad[b], 1);
+  ext_split(er, 0, &ws.man[0][i], &ws.exp[0][i]);
+  if (s == 0) a.status[b] = IRLMX_OK;
+}
+
+__global__ void __launch_bounds__(kSweepThreads) hz_bwd_step_kernel(HzBwdArgs a, HzWs ws, int t, int odd) {
+  const Model& m = a.m;
+  const int S = m.S;
+  const int b = blockIdx.y;
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  if (ws.bad[b]) { hz_nan_state(a, b, t, s); return; }
+  const size_t i = (size_t)b * S + s;
+  const double er = exp(a.reward[i]);
+  int E;
+  const double zsum = hz_row_loop(m, b, s, er, ws.man[odd] + (size_t)b * S, ws.exp[odd] + (size_t)b * S,
+                                  a.pi + hz_pi_row(m, a.T, b, t, s), &E);
+  double zm;
+  int ze;
+  if (a.term && a.term[i]) ext_split(er, 0, &zm, &ze);
+  else ext_split(zsum, E, &zm, &ze);
+  ws.man[odd ^ 1][i] = zm;
+  ws.exp[odd ^ 1][i] = ze;
+  if (t == 0 && a.log_z0) a.log_z0[i] = hz_log_z(zm, ze);
+}
+
+__global__ void hz_fwd_init_kernel(HzFwdArgs a, HzWs ws) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  const int S = a.m.S;
+  if (s >= S) return;
+  const size_t i = (size_t)b * S + s;
+  const double p = a.p0[i];
+  ws.man[0][i] = p;
+  a.svf[i] = p;
+  if (a.svf_t) a.svf_t[(size_t)b * (a.T + 1) * S + s] = p;
+  if (s == 0) a.status[b] = IRLMX_OK;
+}
+
+__global__ void __launch_bounds__(kSweepThreads) hz_fwd_step_kernel(HzFwdArgs a, HzWs ws, int t, int odd) {
+  const Model& m = a.m;
+  const int S = m.S;
+  const int b = blockIdx.y;
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const size_t i = (size_t)b * S + s;
+  const uint8_t* tb = a.term ? a.term + (size_t)b * S : nullptr;
+  const double nd = hz_fwd_state(m, b, s, a.pi + hz_pi_row(m, a.T, b, t, 0), tb, ws.man[odd] + (size_t)b * S);
+  ws.man[odd ^ 1][i] = nd;
+  const double D = __dadd_rn(a.svf[i], nd);
+  a.svf[i] = D;
+  if (a.svf_t) a.svf_t[((size_t)b * (a.T + 1) + t + 1) * S + s] = nd;
+  if (t == a.T - 1 && !isfinite(D)) atomicOr(&a.status[b], IRLMX_NONFINITE);
+}
+
+// ---------------------------------------------------------------------------
+// host-side dispatch
+// ---------------------------------------------------------------------------
+
+// (SPT, KMAX) pairs of the backward: the extended backward's list; every pair
+// compiles without VGPR spills at __launch_bounds__(1024)
+// (tools/kernel_resources.py; the table is in DESIGN.md section 4).
+static constexpr bool hz_pair_ok(int spt, int kmax) {
+  return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt <= 2) || (kmax == 32 && spt == 1);
+}
+// Pairs whose table values stay in registers (at most kHzRegActions actions).
+static constexpr bool hz_pair_reg(int spt, int kmax) { return spt == 1 && kmax == 5; }
+
+template <int S_, int K_, bool R_>
+static void (*hz_bwd_ptr())(HzBwdArgs) {
+  if constexpr (hz_pair_ok(S_, K_) && (!R_ || hz_pair_reg(S_, K_))) return &hz_bwd_fused_kernel<S_, K_, R_>;
+  else return nullptr;
+}
+
+template <bool R_>
+static void (*hz_bwd_fn(int s, int k))(HzBwdArgs) {
+  if (s == 1 && k == 5) return hz_bwd_ptr<1, 5, R_>();
+  if (s == 2 && k == 5) return hz_bwd_ptr<2, 5, R_>();
+  if (s == 4 && k == 5) return hz_bwd_ptr<4, 5, R_>();
+  if (s == 1 && k == 8) return hz_bwd_ptr<1, 8, R_>();
+  if (s == 2 && k == 8) return hz_bwd_ptr<2, 8, R_>();
+  if (s == 1 && k == 16) return hz_bwd_ptr<1, 16, R_>();
+  if (s == 2 && k == 16) return hz_bwd_ptr<2, 16, R_>();
+  if (s == 1 && k == 32) return hz_bwd_ptr<1, 32, R_>();
+  return nullptr;
+}
+
+static void (*hz_fwd_fn(int spt))(HzFwdArgs) {
+  if (spt == 1) return &hz_fwd_fused_kernel<1>;
+  if (spt == 2) return &hz_fwd_fused_kernel<2>;
+  if (spt == 4) return &hz_fwd_fused_kernel<4>;
+  return nullptr;
+}
+
+static size_t hz_fused_lds(const Model& m, int op) {
+  return (size_t)m.S * (op == IRLMX_OP_BACKWARD_HORIZON ? kExtLdsPerState : 2 * sizeof(double));
+}
+
+// The fused shape of a horizon pass: the thread layout of the ordinary fused
+// backward / forward at every width (these passes have no cluster form), when
+// its pair is instantiated, its LDS fits and (several states per thread) the
+// batch is large enough; else one launch per step.
+// Several states per thread (above 1,024 states) only from this many instances
+// on (IRLMX_HORIZON_FUSED_BATCH; tests use 1): one workgroup steps 4,096 states
+// in 24 us where a launch over 16 workgroups takes 11, so below one workgroup
+// per CU the per-sweep shape is the faster one (measured, DESIGN.md section 4
+// "Finite horizon": 64 x 64 fused / per sweep 2.2 at one instance, 1.5 at 64,
+// 0.8 at 256; at one state per thread fused wins at every batch, 0.1 - 0.9).
+static int hz_fused_min_batch() {
+  const int forced_cus = env_int("IRLMX_PLAN_CUS", 0);
+  const int cus = forced_cus > 0 ? forced_cus : device_cus();
+  return env_int("IRLMX_HORIZON_FUSED_BATCH", cus > 0 ? cus : 256);
+}
+
+static bool hz_fused_shape(const Model& m, int op, FusedShape* out) {
+  const bool bwd = op == IRLMX_OP_BACKWARD_HORIZON;
+  if (!fused_shape(m, bwd ? IRLMX_OP_BACKWARD : IRLMX_OP_FORWARD, out, false)) return false;
+  if (bwd && !hz_pair_ok(out->spt, out->kmax)) return false;
+  if (out->spt > 1 && m.B < hz_fused_min_batch()) return false;
+  return hz_fused_lds(m, op) <= kExtLdsMax;
+}
+
+static HzWs hz_carve(const Model& m, int op, void* base) {
+  HzWs w;
+  size_t off = 0;
+  char* p = (char*)base;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += align256(bytes);
+    return (void*)r;
+  };
+  const size_t B = m.B, S = m.S;
+  FusedShape fs;
+  const bool sweep = !hz_fused_shape(m, op, &fs);
+  const bool bwd = op == IRLMX_OP_BACKWARD_HORIZON;
+  w.bad = (int32_t*)take(sweep && bwd ? B * sizeof(int32_t) : 0);
+  for (int i = 0; i < 2; ++i) w.man[i] = (double*)take(sweep ? B * S * sizeof(double) : 0);
+  for (int i = 0; i < 2; ++i) w.exp[i] = (int32_t*)take(sweep && bwd ? B * S * sizeof(int32_t) : 0);
+  w.total = off;
+  return w;
+}
+
+int horizon_check_model(const Model& m, const char* fn) {
+  if (m.dense) {
+    set_error("%s: the finite-horizon passes do not run the DENSE layout (STENCIL5 and ELL only)", fn);
+    return IRLMX_EINVAL;
+  }
+  return 0;
+}
+
+size_t horizon_workspace_bytes(const Model& m, int op) { return hz_carve(m, op, nullptr).total; }
+
+void horizon_plan(const Model& m, int op, int64_t* plan) {
+  FusedShape fs;
+  if (hz_fused_shape(m, op, &fs)) {
+    plan[0] = IRLMX_SHAPE_FUSED;
+    plan[5] = fs.spt;
+    plan[7] = fs.threads;
+    plan[8] = 1;
+    plan[9] = (int64_t)hz_fused_lds(m, op);
+    return;
+  }
+  plan[0] = IRLMX_SHAPE_SWEEP;
+  plan[5] = 1;  // one state per lane; the launch count is the horizon
+  plan[7] = kSweepThreads;
+}
+
+static int hz_check_call(const Model& m, const char* fn, int op, int32_t horizon, size_t bytes, void* ws) {
+  if (horizon < 1 || horizon > kHzMaxHorizon) {
+    set_error("%s: horizon %d outside [1, %d]", fn, horizon, kHzMaxHorizon);
+    return IRLMX_EINVAL;
+  }
+  const size_t need = hz_carve(m, op, nullptr).total;
+  if (bytes < need || (need && !ws)) {
+    set_error("workspace too small: need %zu bytes, got %zu", need, bytes);
+    return IRLMX_EWORKSPACE;
+  }
+  return 0;
+}
+
+}  // namespace irlmx
+
+using namespace irlmx;
+
+extern "C" int irlmx_backward_maxent_horizon(const irlmx_mdp* mdp, const double* reward, const uint8_t* terminal,
+                                             int32_t horizon, double* p_action_t, double* log_z0, int32_t* status,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "backward_maxent_horizon";
+  if (int rc = validate(mdp)) return rc;
+  const Model m = make_model(mdp);
+  if (int rc = horizon_check_model(m, fn)) return rc;
+  if (int rc = need_all(fn, {{reward, "reward"}, {p_action_t, "p_action_t"}, {status, "status"}})) return rc;
+  if (int rc = hz_check_call(m, fn, IRLMX_OP_BACKWARD_HORIZON, horizon, workspace_bytes, workspace)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HzBwdArgs a{m, reward, terminal, horizon, p_action_t, log_z0, status};
+  FusedShape fs;
+  if (hz_fused_shape(m, IRLMX_OP_BACKWARD_HORIZON, &fs)) {
+    void (*kfn)(HzBwdArgs) = nullptr;
+    if (m.A <= kHzRegActions) kfn = hz_bwd_fn<true>(fs.spt, fs.kmax);
+    if (!kfn) kfn = hz_bwd_fn<false>(fs.spt, fs.kmax);
+    if (!kfn) { set_error("no horizon backward fused kernel for spt=%d kmax=%d", fs.spt, fs.kmax); return IRLMX_EINVAL; }
+    const size_t lds = hz_fused_lds(m, IRLMX_OP_BACKWARD_HORIZON);
+    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
+    hipLaunchKernelGGL(kfn, dim3(m.B), dim3(fs.threads), lds, st, a);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "hz_bwd_fused_kernel");
+  }
+  HzWs ws = hz_carve(m, IRLMX_OP_BACKWARD_HORIZON, workspace);
+  hipError_t e = hipMemsetAsync(ws.bad, 0, (size_t)m.B * sizeof(int32_t), st);
+  if (e != hipSuccess) return hip_fail(e, "workspace memset");
+  count_event(IRLMX_CTR_SWEEP_CALLS);
+  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  hipLaunchKernelGGL(hz_bwd_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
+  for (int it = 0; it < horizon; ++it)
+    hipLaunchKernelGGL(hz_bwd_step_kernel, g, dim3(kSweepThreads), 0, st, a, ws, horizon - 1 - it, it & 1);
+  e = hipGetLastError();
+  return e == hipSuccess ? 0 : hip_fail(e, "horizon backward");
+}
+
+extern "C" int irlmx_forward_svf_horizon(const irlmx_mdp* mdp, const double* p_initial, const uint8_t* terminal,
+                                         const double* p_action_t, int32_t horizon, double* svf, double* svf_t,
+                                         int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "forward_svf_horizon";
+  if (int rc = validate(mdp)) return rc;
+  const Model m = make_model(mdp);
+  if (int rc = horizon_check_model(m, fn)) return rc;
+  if (!m.stencil && (!m.col_idx || !m.col_val || m.Kc <= 0)) {
+    set_error("ELL column form missing");
+    return IRLMX_EINVAL;
+  }
+  if (int rc = need_all(fn, {{p_initial, "p_initial"}, {p_action_t, "p_action_t"}, {svf, "svf"}, {status, "status"}}))
+    return rc;
+  if (int rc = hz_check_call(m, fn, IRLMX_OP_FORWARD_HORIZON, horizon, workspace_bytes, workspace)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HzFwdArgs a{m, p_initial, terminal, p_action_t, horizon, svf, svf_t, status};
+  FusedShape fs;
+  if (hz_fused_shape(m, IRLMX_OP_FORWARD_HORIZON, &fs)) {
+    void (*kfn)(HzFwdArgs) = hz_fwd_fn(fs.spt);
+    if (!kfn) { set_error("no horizon forward fused kernel for spt=%d", fs.spt); return IRLMX_EINVAL; }
+    const size_t lds = hz_fused_lds(m, IRLMX_OP_FORWARD_HORIZON);
+    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
+    hipLaunchKernelGGL(kfn, dim3(m.B), dim3(fs.threads), lds, st, a);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "hz_fwd_fused_kernel");
+  }
+  HzWs ws = hz_carve(m, IRLMX_OP_FORWARD_HORIZON, workspace);
+  count_event(IRLMX_CTR_SWEEP_CALLS);
+  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  hipLaunchKernelGGL(hz_fwd_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
+  for (int t = 0; t < horizon; ++t)
+    hipLaunchKernelGGL(hz_fwd_step_kernel, g, dim3(kSweepThreads), 0, st, a, ws, t, t & 1);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : hip_fail(e, "horizon forward");
+}

@@ -25,6 +25,8 @@ SUCCESS = 0
 OK, NONFINITE, MAXITER = 0, 1, 2
 OP_BACKWARD, OP_FORWARD, OP_SOFT_BACKWARD, OP_VALUE_ITERATION = 1, 2, 3, 4
 OP_POLICY_EVALUATION = 6   # (5 is not an op: the library has always answered "unknown op 5")
+OP_BACKWARD_HORIZON, OP_FORWARD_HORIZON = 8, 9   # (7 is not an op either)
+HORIZON_MAX = 1 << 20
 PLAN_NO_RESCALE = 0x100
 PLAN_EXTENDED_RANGE = 0x200
 PROPS_KNOWN, PROP_COMPACT, PROP_ELL_SORTED = 0x40000000, 0x1, 0x2
@@ -88,6 +90,8 @@ SIGNATURES = {
     "irlmx_value_iteration_numpy_order": (ctypes.c_int, [_MDP, _P, _D, _D, _I32, _I64, _P, _P, _P, _P]),
     "irlmx_value_iteration": (ctypes.c_int, [_MDP, _P, _D, _D, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
     "irlmx_policy_evaluation": (ctypes.c_int, [_MDP, _P, _P, _P, _D, _D, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "irlmx_backward_maxent_horizon": (ctypes.c_int, [_MDP, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "irlmx_forward_svf_horizon": (ctypes.c_int, [_MDP, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "irlmx_rollout": (ctypes.c_int, [_MDP, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "irlmx_demo_statistics": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "irlmx_demo_log_likelihood": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),

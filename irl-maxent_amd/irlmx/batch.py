@@ -52,6 +52,15 @@ that can be co-resident in one persistent launch (and then synchronises the
 stream); a rerun set that would need more sequential launches than
 ``IRLMX_EXT_GRID_MAX_LAUNCHES`` takes one launch per sweep, as every model
 between 4096 and 8192 states does.
+
+Finite horizon (``horizon=T``, non-causal only): for models without a terminal
+state and demonstrations cut after T steps (``ops.rollout``'s truncated
+trajectories).  ``backward()`` returns the time-indexed policy [n, T, S, A]
+(``ops.backward_maxent_horizon``; n * T * S * A * 8 bytes: 17 MB for one 64x64
+instance at T = 128) and ``forward()`` sums the T + 1 marginals
+(``ops.forward_svf_horizon``), both fully asynchronous; ``terminal`` may be
+empty; ``extended_range`` is ignored, the pass always keeps one exponent per
+state.
 """
 
 import numpy as np
@@ -77,7 +86,7 @@ def terminal_reward(terminal, n_states, batch=1, device=None):
 class BatchedMaxEnt:
     def __init__(self, mdp: DeviceMDP, e_features, p_initial, terminal, features=None, lr0=0.2,
                  eps_esvf=1e-5, theta0=1.0, rescale=True, causal=False, discount=None, eps_lap=1e-5,
-                 optimizer=None, extended_range=False):
+                 optimizer=None, extended_range=False, horizon=None):
         """``theta0``: a float (the reference's Constant init, optimizer.py:369-398) or
         an array [F] or [B, F] (e.g. drawn with the reference's Uniform init,
         optimizer.py:334-366).  ``optimizer``: an irlmx.optim optimiser (default
@@ -89,7 +98,18 @@ class BatchedMaxEnt:
         recomputed with the extended pass and spliced in.  In a gridworld a zero
         is either underflow or a state that cannot reach a terminal; in the
         second case the rerun returns the same zero.  The check costs one device
-        reduction and one host read per step."""
+        reduction and one host read per step.
+        ``horizon``: an int T >= 1 runs the finite-horizon passes (module
+        docstring); ``terminal`` may then be empty; ValueError with
+        ``causal=True``."""
+        if horizon is not None:
+            if causal:
+                raise ValueError("horizon applies to the non-causal model only (a finite-horizon soft value "
+                                 "iteration is not implemented)")
+            if int(horizon) != horizon or not 1 <= int(horizon) <= (1 << 20):
+                raise ValueError(f"horizon must be an integer in [1, 2^20], got {horizon!r}")
+            horizon = int(horizon)
+        self.horizon = horizon
         if extended_range not in (False, True, "auto"):
             raise ValueError(f"extended_range must be False, True or 'auto', got {extended_range!r}")
         self.extended_range = extended_range
@@ -109,7 +129,8 @@ class BatchedMaxEnt:
             n_f = f.shape[-1]
         self.e_features = torch.as_tensor(e_features, dtype=torch.float64, device=dev).reshape(B, n_f)
         self.p_initial = torch.as_tensor(p_initial, dtype=torch.float64, device=dev).reshape(B, S)
-        self.terminal = ops.terminal_mask(terminal, S, batch=B, device=dev)
+        self.terminal = ops.terminal_mask(np.asarray(terminal, dtype=np.int64) if np.size(terminal) == 0 else terminal,
+                                          S, batch=B, device=dev)
         self.causal = causal
         self.phi = None
         if causal:
@@ -207,9 +228,12 @@ class BatchedMaxEnt:
         return torch.bmm(svf.unsqueeze(1), features).squeeze(1)
 
     def backward(self):
-        """Policy [n, S, A] of the working set (maxent.py:119-159 / 279-341)."""
+        """Policy [n, S, A] of the working set (maxent.py:119-159 / 279-341); with
+        ``horizon=T`` the time-indexed policy [n, T, S, A]."""
         r = self.reward(self._theta_w(), self._w("features"))
         mdp = self._w("mdp")
+        if self.horizon is not None:
+            return ops.backward_maxent_horizon(mdp, r, self.horizon, self._w("terminal"))
         if self.causal:
             pi, _, k, _ = ops.soft_backward(mdp, r, self._w("phi"), self.discount, self.eps_lap)
             self.last_backward_sweeps = self._scatter(k)
@@ -227,7 +251,10 @@ class BatchedMaxEnt:
         return pi
 
     def forward(self, pi):
-        """``(svf [n, S], sweeps [n], status [n])`` of the working set (maxent.py:63-114)."""
+        """``(svf [n, S], sweeps [n], status [n])`` of the working set (maxent.py:63-114);
+        with ``horizon=T`` the sum of the T + 1 marginals, sweeps = T."""
+        if self.horizon is not None:
+            return ops.forward_svf_horizon(self._w("mdp"), self._w("p_initial"), pi, self._w("terminal"))
         return ops.forward_svf(self._w("mdp"), self._w("p_initial"), self._w("terminal"), pi, self.eps_esvf)
 
     def update(self, svf):
@@ -264,6 +291,7 @@ class BatchedMaxEnt:
         is their result); p0 and the terminals are this object's own
         (ops.expected_value_difference).  Reads theta only: theta, the step
         counter, the active set and the compaction state stay as they are."""
+        self._stationary_only("expected_value_difference")
         work, sweeps = self._work, self.last_backward_sweeps
         self._work = None          # the full batch, in original order
         try:
@@ -276,6 +304,12 @@ class BatchedMaxEnt:
         return ops.expected_value_difference(self.mdp, r.contiguous(), pi, self.p_initial, discount, self.terminal,
                                              eps)[0]
 
+    def _stationary_only(self, what):
+        if self.horizon is not None:
+            raise NotImplementedError(f"{what} takes a stationary policy; with horizon={self.horizon} the policy is "
+                                      "time-indexed [T, S, A] and its rollouts, log-likelihood and policy evaluation "
+                                      "are not implemented")
+
     def log_likelihood(self, states, actions, lengths):
         """Mean per-trajectory log-likelihood of stored demonstrations (``states``
         [B, N, L + 1], ``actions`` [B, N, L], ``lengths`` [B, N], as
@@ -285,6 +319,7 @@ class BatchedMaxEnt:
         needs no true reward; -inf where a demonstration takes an action the
         policy gives probability 0.  Reads theta only: theta, the step counter,
         the active set and the compaction state stay as they are."""
+        self._stationary_only("log_likelihood")
         work, sweeps = self._work, self.last_backward_sweeps
         self._work = None          # the full batch, in original order
         try:

@@ -31,13 +31,15 @@ def _workspace(mdp, op):
 PLAN_FIELDS = ("shape", "R", "G", "C", "per_launch", "spt", "layout", "threads", "launches", "lds_bytes")
 SHAPES = {0: "fused", 1: "cluster", 2: "sweep", 3: "dense", 4: "dense-gemm", 5: "grid", 6: "dense-grid"}
 _OPS = {"backward": _lib.OP_BACKWARD, "forward": _lib.OP_FORWARD, "soft_backward": _lib.OP_SOFT_BACKWARD,
-        "value_iteration": _lib.OP_VALUE_ITERATION, "policy_evaluation": _lib.OP_POLICY_EVALUATION}
+        "value_iteration": _lib.OP_VALUE_ITERATION, "policy_evaluation": _lib.OP_POLICY_EVALUATION,
+        "backward_horizon": _lib.OP_BACKWARD_HORIZON, "forward_horizon": _lib.OP_FORWARD_HORIZON}
 _OPS.update({code: code for code in list(_OPS.values())})   # the _lib.OP_* codes themselves are accepted too
 
 
 def execution_plan(mdp, op, rescale=True, extended_range=False):
     """The kernel plan a call of ``op`` ("backward", "forward", "soft_backward",
-    "value_iteration", "policy_evaluation", or its ``_lib.OP_*`` code) on ``mdp``
+    "value_iteration", "policy_evaluation", "backward_horizon",
+    "forward_horizon", or its ``_lib.OP_*`` code) on ``mdp``
     runs on the current device (irlmx_execution_plan):
     shape, tile rows R, ghost rows G, tiles per instance C, instances per launch,
     states per lane, in-tile layout, threads, sequential launches, LDS bytes.
@@ -324,6 +326,73 @@ def policy_evaluation(mdp, reward, p_action, discount, terminal=None, eps=1e-3, 
     return v, iters, status
 
 
+def _optional_mask(terminal, mdp):
+    if terminal is None:
+        return None
+    return terminal.to(device=mdp.device, dtype=torch.uint8).reshape(mdp.batch, mdp.n_states).contiguous()
+
+
+def backward_maxent_horizon(mdp, reward, horizon, terminal=None, return_log_z0=False):
+    """Time-indexed local action probabilities ``pi_t`` [B, T, S, A] of the
+    finite-horizon MaxEnt model with ``T = horizon`` steps
+    (irlmx_backward_maxent_horizon): from ``Z_T = exp(r)``, for t = T-1 .. 0,
+    ``za_t = exp(r) * (P_a Z_{t+1})``, ``Z_t = sum_a za_t`` and ``pi_t = za_t /
+    Z_t``.  No terminal state is needed (``terminal=None``); with a uint8
+    [B, S] mask (:func:`terminal_mask`) those states are absorbing, ``Z_t =
+    exp(r)``.  Every partition value carries its own exponent, as in
+    :func:`backward_maxent_extended`, so the policy is finite wherever a
+    successor has weight.  ``return_log_z0``: returns ``(pi_t, log_z0 [B, S])``,
+    the log partition function of the T-step paths from each state.
+
+    Memory: the result is ``B * T * S * A * 8`` bytes -- 17 MB for one 64x64
+    instance at T = 128.  STENCIL5 and ELL models; ``execution_plan(mdp,
+    "backward_horizon")`` names the shape."""
+    lib = _lib.load()
+    B, S, A, T = mdp.batch, mdp.n_states, mdp.n_actions, int(horizon)
+    r = _f64(reward, mdp, (B, S))
+    term = _optional_mask(terminal, mdp)
+    ok = 1 <= T <= _lib.HORIZON_MAX      # (else the call below raises: nothing of size T is allocated)
+    pi = torch.empty((B, T if ok else 1, S, A), dtype=torch.float64, device=mdp.device)
+    lz = torch.empty((B, S), dtype=torch.float64, device=mdp.device) if return_log_z0 else None
+    status = torch.empty(B, dtype=torch.int32, device=mdp.device)
+    ws, n = _workspace(mdp, _lib.OP_BACKWARD_HORIZON)
+    _lib.check(lib.irlmx_backward_maxent_horizon(mdp.struct(), _lib.ptr(r), _lib.ptr(term), T, _lib.ptr(pi),
+                                                 _lib.ptr(lz), _lib.ptr(status), _lib.ptr(ws), n,
+                                                 _lib.stream_ptr(mdp.device)), "backward_maxent_horizon")
+    return (pi, lz) if return_log_z0 else pi
+
+
+def forward_svf_horizon(mdp, p_initial, p_action_t, terminal=None, return_marginals=False):
+    """Expected state visitation of T steps under the time-indexed policy
+    ``p_action_t`` [B, T, S, A] (irlmx_forward_svf_horizon): ``d_0 = p0``,
+    ``d_{t+1} = sum_a P_a^T (pi_t[:, a] * d_t)`` with the rows of terminal
+    states cleared, and ``svf = d_0 + .. + d_T``.
+
+    Returns ``(svf [B, S], sweeps [B] int64 -- T for every instance --, status
+    [B] int32)`` and with ``return_marginals`` a fourth entry ``svf_t`` [B, T + 1,
+    S], the marginals (``B * (T + 1) * S * 8`` bytes).  Status is
+    ``_lib.NONFINITE`` exactly where ``svf`` holds a non-finite entry.  Without
+    terminals ``svf`` sums to T + 1."""
+    lib = _lib.load()
+    B, S, A = mdp.batch, mdp.n_states, mdp.n_actions
+    pi = torch.as_tensor(p_action_t, dtype=torch.float64, device=mdp.device)
+    if pi.dim() != 4 or pi.shape[0] != B or tuple(pi.shape[2:]) != (S, A):
+        raise ValueError(f"p_action_t must be [B = {B}, T, S = {S}, A = {A}], got {tuple(pi.shape)}")
+    pi = pi.contiguous()
+    T = int(pi.shape[1])
+    p0 = _f64(p_initial, mdp, (B, S))
+    term = _optional_mask(terminal, mdp)
+    svf = torch.empty((B, S), dtype=torch.float64, device=mdp.device)
+    marg = torch.empty((B, T + 1, S), dtype=torch.float64, device=mdp.device) if return_marginals else None
+    status = torch.empty(B, dtype=torch.int32, device=mdp.device)
+    ws, n = _workspace(mdp, _lib.OP_FORWARD_HORIZON)
+    _lib.check(lib.irlmx_forward_svf_horizon(mdp.struct(), _lib.ptr(p0), _lib.ptr(term), _lib.ptr(pi), T, _lib.ptr(svf),
+                                             _lib.ptr(marg), _lib.ptr(status), _lib.ptr(ws), n,
+                                             _lib.stream_ptr(mdp.device)), "forward_svf_horizon")
+    sweeps = torch.full((B,), T, dtype=torch.int64, device=mdp.device)
+    return (svf, sweeps, status, marg) if return_marginals else (svf, sweeps, status)
+
+
 def _row_targets(mdp):
     """Target state of every stored slot, int64 [tables, K, S] on the device."""
     if mdp.layout == _lib.LAYOUT_ELL:
@@ -548,6 +617,6 @@ def stochastic_policy(successor, weighted_value):
     return out
 
 
-__all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "backward_maxent_extended", "forward_svf", "soft_backward",
+__all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "backward_maxent_extended", "backward_maxent_horizon", "forward_svf", "forward_svf_horizon", "soft_backward",
            "value_iteration", "policy_evaluation", "expected_value_difference", "rollout", "rollout_seeds",
            "demo_statistics", "demo_log_likelihood", "RolloutResult", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]

@@ -35,6 +35,12 @@ Deliberate differences (documented in DESIGN.md):
   One workgroup up to 4096 states, one persistent launch from 8192 states on
   (a 256 x 256 grid: 131,072 sweeps in one launch), one launch per sweep in
   between (``ops.backward_maxent_extended``).
+
+Beyond the reference: ``local_action_probabilities_horizon``,
+``compute_expected_svf_horizon`` and ``irl_horizon`` are the finite-horizon
+form of the same model (``ops.backward_maxent_horizon``,
+``ops.forward_svf_horizon``), for worlds without a terminal state
+(``terminal=[]``) and demonstrations of a fixed length.
 """
 
 import os
@@ -48,7 +54,8 @@ from irlmx import DeviceMDP, ops
 __all__ = ["feature_expectation_from_trajectories", "initial_probabilities_from_trajectories",
            "expected_svf_from_policy", "local_action_probabilities", "compute_expected_svf",
            "expected_svf", "irl", "softmax", "local_causal_action_probabilities",
-           "compute_expected_causal_svf", "irl_causal"]
+           "compute_expected_causal_svf", "irl_causal", "local_action_probabilities_horizon",
+           "compute_expected_svf_horizon", "irl_horizon"]
 
 
 def _rescale():
@@ -203,6 +210,48 @@ def irl(p_transition, features, terminal, trajectories, optim, init, eps=1e-4, e
     def svf_fn(m, reward, term, p0):
         pi = _backward(m, reward, term)
         svf, _, _ = _forward(m, p0, term, pi, eps_esvf)
+        return _host(svf)
+
+    return _irl_loop(mdp, features, terminal, trajectories, optim, init, eps, svf_fn)
+
+
+# -- finite horizon (no reference counterpart) ---------------------------------
+
+def _horizon_mask(mdp, terminal):
+    """The terminal mask, or None for an empty ``terminal`` (no terminal state)."""
+    return ops.terminal_mask(terminal, mdp.n_states, device=mdp.device) if np.size(terminal) else None
+
+
+def local_action_probabilities_horizon(p_transition, terminal, reward, horizon):
+    """Time-indexed local action probabilities [T, S, A] of the finite-horizon
+    MaxEnt model with ``T = horizon`` steps (``ops.backward_maxent_horizon``):
+    ``terminal`` may be ``[]``.  T * S * A * 8 bytes: 17 MB on a 64x64 grid at
+    T = 128."""
+    mdp = _model(p_transition)
+    return _host(ops.backward_maxent_horizon(mdp, reward, horizon, _horizon_mask(mdp, terminal)))
+
+
+def compute_expected_svf_horizon(p_transition, p_initial, terminal, reward, horizon):
+    """Expected state visitation over the T + 1 states of a ``horizon``-step
+    trajectory: the finite-horizon backward then forward pass
+    (``ops.forward_svf_horizon``).  Sums to T + 1 without terminals."""
+    mdp = _model(p_transition)
+    term = _horizon_mask(mdp, terminal)
+    pi = ops.backward_maxent_horizon(mdp, reward, horizon, term)
+    svf, _, _ = ops.forward_svf_horizon(mdp, p_initial, pi, term)
+    return _host(svf)
+
+
+def irl_horizon(p_transition, features, terminal, trajectories, optim, init, horizon, eps=1e-4):
+    """MaxEnt IRL with the finite-horizon model: ``irl``'s gradient ascent, the
+    expected visitation from ``compute_expected_svf_horizon``.  For
+    demonstrations of ``horizon`` steps each; ``terminal`` may be ``[]``."""
+    mdp = _model(p_transition)
+    term_h = _horizon_mask(mdp, terminal)
+
+    def svf_fn(m, reward, term, p0):
+        pi = ops.backward_maxent_horizon(m, reward, horizon, term_h)
+        svf, _, _ = ops.forward_svf_horizon(m, p0, pi, term_h)
         return _host(svf)
 
     return _irl_loop(mdp, features, terminal, trajectories, optim, init, eps, svf_fn)

@@ -28,6 +28,12 @@
 //    the backward-only flags, and every validation path of
 //    irlmx_policy_evaluation (NULL arrays, discount outside [0, 1] or NaN,
 //    short workspace);
+//  * the finite-horizon passes (horizon.hip): the plan and workspace of
+//    IRLMX_OP_BACKWARD_HORIZON and IRLMX_OP_FORWARD_HORIZON for every stencil
+//    and ELL model above (fused or per sweep), their refusal of DENSE tables
+//    and of the backward-only flags, and every validation path of
+//    irlmx_backward_maxent_horizon and irlmx_forward_svf_horizon (NULL arrays,
+//    the optional ones, a horizon outside [1, 2^20], short workspace);
 //  * the demonstration calls (rollout.hip): every validation path of
 //    irlmx_rollout (NULL arrays, n_traj, max_len below 1 and above its cap,
 //    states without actions, DENSE tables), irlmx_demo_statistics and
@@ -266,6 +272,53 @@ static void policy_eval_plan_and_workspace(const irlmx_mdp& m, const char* what)
         "%s: no-rescale flag on policy evaluation", what);
 }
 
+static long long g_hz_shapes[3];
+
+// The finite-horizon passes' plan and workspace for one model
+// (IRLMX_OP_BACKWARD_HORIZON, IRLMX_OP_FORWARD_HORIZON): fused or per sweep,
+// never a persistent shape; refused on DENSE tables.
+static void horizon_plan_and_workspace(const irlmx_mdp& m, const char* what) {
+  for (int op : {IRLMX_OP_BACKWARD_HORIZON, IRLMX_OP_FORWARD_HORIZON}) {
+    const bool bwd = op == IRLMX_OP_BACKWARD_HORIZON;
+    int64_t p[IRLMX_PLAN_LEN];
+    for (auto& v : p) v = -7;
+    const int rc = irlmx_execution_plan(&m, op, p);
+    const size_t ws = irlmx_workspace_bytes(&m, op);
+    if (m.layout == IRLMX_LAYOUT_DENSE) {
+      CHECK(rc == IRLMX_EINVAL && strstr(irlmx_last_error(), "DENSE"), "%s: horizon plan %d of a DENSE table rc %d", what, op,
+            rc);
+      CHECK(ws == 0, "%s: horizon workspace %d of a DENSE table %zu", what, op, ws);
+      continue;
+    }
+    CHECK(rc == 0, "%s: horizon plan %d rc %d (%s)", what, op, rc, irlmx_last_error());
+    if (rc) continue;
+    const size_t S = (size_t)m.n_states, B = (size_t)m.batch;
+    const size_t K = m.layout == IRLMX_LAYOUT_STENCIL5 ? 5 : (size_t)(bwd ? m.k_row : m.k_col);
+    CHECK(p[0] == IRLMX_SHAPE_FUSED || p[0] == IRLMX_SHAPE_SWEEP, "%s: horizon shape %lld", what, (long long)p[0]);
+    CHECK(p[1] == 0 && p[2] == 0 && p[3] == 0 && p[4] == 0 && p[6] == 0, "%s: horizon plan cluster fields", what);
+    if (p[0] == IRLMX_SHAPE_FUSED) {
+      ++g_hz_shapes[0];
+      CHECK(S <= 4096 && K <= 32, "%s: horizon fused at S %zu K %zu", what, S, K);
+      CHECK(p[7] >= 64 && p[7] <= 1024 && p[7] % 64 == 0, "%s: horizon fused threads %lld", what, (long long)p[7]);
+      CHECK(p[5] >= 1 && p[5] <= 4 && p[5] * p[7] >= (int64_t)S, "%s: horizon fused spt %lld", what, (long long)p[5]);
+      CHECK(p[8] == 1 && p[9] == (int64_t)((bwd ? 24 : 16) * S) && p[9] <= 160 * 1024, "%s: horizon fused LDS %lld", what,
+            (long long)p[9]);
+      CHECK(ws == 0, "%s: horizon fused workspace %zu", what, ws);
+    } else {
+      ++g_hz_shapes[2];
+      CHECK(p[5] == 1 && p[7] == 256 && p[8] == 0 && p[9] == 0, "%s: horizon sweep plan", what);
+      const size_t floor = B * S * (bwd ? 24 : 16);
+      CHECK(ws >= floor && ws <= floor + 8 * 256 && ws % 256 == 0, "%s: horizon workspace %zu (floor %zu)", what, ws, floor);
+    }
+    CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_EXTENDED_RANGE, p) == IRLMX_EINVAL &&
+              strstr(irlmx_last_error(), "IRLMX_OP_BACKWARD only"),
+          "%s: extended flag on a horizon op", what);
+    CHECK(irlmx_workspace_bytes(&m, op | IRLMX_PLAN_EXTENDED_RANGE) == 0, "%s: extended workspace of a horizon op", what);
+    CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_NO_RESCALE, p) == IRLMX_EINVAL && strstr(irlmx_last_error(), "NO_RESCALE"),
+          "%s: no-rescale flag on a horizon op", what);
+  }
+}
+
 static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
   for (int op = IRLMX_OP_BACKWARD; op <= IRLMX_OP_VALUE_ITERATION; ++op) {
     char what[160];
@@ -282,6 +335,7 @@ static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
       CHECK(p2[0] != IRLMX_SHAPE_CLUSTER, "%s: rescale=0 backward planned on the cluster shape", what);
       extended_plan_and_workspace(m, what);
       policy_eval_plan_and_workspace(m, what);
+      horizon_plan_and_workspace(m, what);
     }
     const size_t ws = irlmx_workspace_bytes(&m, op);
     const size_t floor = (op == IRLMX_OP_BACKWARD || op == IRLMX_OP_FORWARD)
@@ -306,6 +360,18 @@ static int run_pe(const irlmx_mdp* m, void* reward, void* pi, void* term, double
                   void* status, void* ws, size_t n) {
   return irlmx_policy_evaluation(m, (const double*)reward, (const double*)pi, (const uint8_t*)term, discount, 1e-3, 0,
                                  (double*)value, (int64_t*)iters, (int32_t*)status, ws, n, nullptr);
+}
+
+static int run_hzb(const irlmx_mdp* m, void* reward, void* term, int horizon, void* pi, void* lz, void* status, void* ws,
+                   size_t n) {
+  return irlmx_backward_maxent_horizon(m, (const double*)reward, (const uint8_t*)term, horizon, (double*)pi, (double*)lz,
+                                       (int32_t*)status, ws, n, nullptr);
+}
+
+static int run_hzf(const irlmx_mdp* m, void* p0, void* term, void* pi, int horizon, void* svf, void* svf_t, void* status,
+                   void* ws, size_t n) {
+  return irlmx_forward_svf_horizon(m, (const double*)p0, (const uint8_t*)term, (const double*)pi, horizon, (double*)svf,
+                                   (double*)svf_t, (int32_t*)status, ws, n, nullptr);
 }
 
 static int run_roll(const irlmx_mdp* m, int n_traj, int max_len, void* pi, void* term, void* start, void* seed,
@@ -415,6 +481,55 @@ static void error_paths() {
     CHECK(p[0] == IRLMX_SHAPE_SWEEP, "policy evaluation plan K = 40: shape %lld", (long long)p[0]);
     expect(irlmx_execution_plan(&good, IRLMX_OP_POLICY_EVALUATION + 1, p), IRLMX_EINVAL, "unknown op 7", "op 7");
     expect(irlmx_execution_plan(&good, 5, p), IRLMX_EINVAL, "unknown op 5", "op 5 (never an op)");
+  }
+  {  // irlmx_backward_maxent_horizon, irlmx_forward_svf_horizon: every validation path, in the order the entries check them
+    irlmx_mdp big = stencil(128, 40, 4, 2, 0);  // per sweep: its workspace is not empty (a fused model needs none)
+    const size_t nb = irlmx_workspace_bytes(&big, IRLMX_OP_BACKWARD_HORIZON);
+    const size_t nf = irlmx_workspace_bytes(&big, IRLMX_OP_FORWARD_HORIZON);
+    CHECK(nb > 0 && nf > 0 && nb > nf, "horizon workspaces of a per-sweep model: %zu, %zu", nb, nf);
+    CHECK(irlmx_workspace_bytes(&good, IRLMX_OP_BACKWARD_HORIZON) == 0 && irlmx_workspace_bytes(&good, IRLMX_OP_FORWARD_HORIZON) == 0,
+          "horizon workspaces of a fused model");
+    expect(run_hzb(nullptr, f, f, 8, f, f, f, f, nb), IRLMX_EINVAL, "mdp is NULL", "horizon backward null mdp");
+    expect(run_hzf(nullptr, f, f, f, 8, f, f, f, f, nf), IRLMX_EINVAL, "mdp is NULL", "horizon forward null mdp");
+    for (const Bad& b : bad) {
+      expect(run_hzb(&b.m, f, f, 8, f, f, f, f, nb), IRLMX_EINVAL, b.msg, b.name);
+      expect(run_hzf(&b.m, f, f, f, 8, f, f, f, f, nf), IRLMX_EINVAL, b.msg, b.name);
+      CHECK(irlmx_workspace_bytes(&b.m, IRLMX_OP_BACKWARD_HORIZON) == 0 && irlmx_workspace_bytes(&b.m, IRLMX_OP_FORWARD_HORIZON) == 0,
+            "%s: horizon workspace of an invalid model", b.name);
+    }
+    irlmx_mdp d = dense(25, 4, 1);
+    expect(run_hzb(&d, f, f, 8, f, f, f, f, nb), IRLMX_EINVAL, "backward_maxent_horizon: the finite-horizon passes do not run the DENSE",
+           "horizon backward dense");
+    expect(run_hzf(&d, f, f, f, 8, f, f, f, f, nf), IRLMX_EINVAL, "forward_svf_horizon: the finite-horizon passes do not run the DENSE",
+           "horizon forward dense");
+    irlmx_mdp nocol = ell(25, 4, 3, 3, 1);
+    nocol.col_idx = nullptr;
+    expect(run_hzf(&nocol, f, f, f, 8, f, f, f, f, nf), IRLMX_EINVAL, "ELL column form missing", "horizon forward without columns");
+    expect(run_hzb(&big, nullptr, f, 8, f, f, f, f, nb), IRLMX_EINVAL, "backward_maxent_horizon: reward is NULL", "horizon null reward");
+    expect(run_hzb(&big, f, f, 8, nullptr, f, f, f, nb), IRLMX_EINVAL, "p_action_t is NULL", "horizon backward null p_action_t");
+    expect(run_hzb(&big, f, f, 8, f, f, nullptr, f, nb), IRLMX_EINVAL, "status is NULL", "horizon backward null status");
+    expect(run_hzf(&big, nullptr, f, f, 8, f, f, f, f, nf), IRLMX_EINVAL, "forward_svf_horizon: p_initial is NULL", "horizon null p_initial");
+    expect(run_hzf(&big, f, f, nullptr, 8, f, f, f, f, nf), IRLMX_EINVAL, "p_action_t is NULL", "horizon forward null p_action_t");
+    expect(run_hzf(&big, f, f, f, 8, nullptr, f, f, f, nf), IRLMX_EINVAL, "svf is NULL", "horizon null svf");
+    expect(run_hzf(&big, f, f, f, 8, f, f, nullptr, f, nf), IRLMX_EINVAL, "status is NULL", "horizon forward null status");
+    for (int h : {0, -1, (1 << 20) + 1}) {
+      expect(run_hzb(&big, f, f, h, f, f, f, f, nb), IRLMX_EINVAL, "outside [1, 1048576]", "horizon backward out of range");
+      expect(run_hzf(&big, f, f, f, h, f, f, f, f, nf), IRLMX_EINVAL, "outside [1, 1048576]", "horizon forward out of range");
+    }
+    // terminal, log_z0 and svf_t may be NULL: the calls get as far as the workspace check
+    expect(run_hzb(&big, f, nullptr, 1 << 20, f, nullptr, f, f, nb - 1), IRLMX_EWORKSPACE, "workspace too small",
+           "horizon backward short workspace (terminal and log_z0 NULL are legal)");
+    expect(run_hzf(&big, f, nullptr, f, 1 << 20, f, nullptr, f, f, nf - 1), IRLMX_EWORKSPACE, "workspace too small",
+           "horizon forward short workspace (terminal and svf_t NULL are legal)");
+    expect(run_hzb(&big, f, f, 8, f, f, f, nullptr, nb), IRLMX_EWORKSPACE, "workspace too small", "horizon backward null workspace");
+    expect(run_hzf(&big, f, f, f, 8, f, f, f, nullptr, nf), IRLMX_EWORKSPACE, "workspace too small", "horizon forward null workspace");
+    int64_t p[IRLMX_PLAN_LEN];
+    irlmx_mdp wide = ell(100, 4, 40, 3, 2);  // more row slots than any fused kernel holds: the backward per sweep
+    expect(irlmx_execution_plan(&wide, IRLMX_OP_BACKWARD_HORIZON, p), IRLMX_OK, "", "horizon backward plan K = 40");
+    CHECK(p[0] == IRLMX_SHAPE_SWEEP, "horizon backward plan K = 40: shape %lld", (long long)p[0]);
+    expect(irlmx_execution_plan(&wide, IRLMX_OP_FORWARD_HORIZON, p), IRLMX_OK, "", "horizon forward plan K_c = 3");
+    CHECK(p[0] == IRLMX_SHAPE_FUSED, "horizon forward plan K_c = 3: shape %lld", (long long)p[0]);
+    expect(irlmx_execution_plan(&good, IRLMX_OP_FORWARD_HORIZON + 1, p), IRLMX_EINVAL, "unknown op 10", "op 10");
   }
   {  // irlmx_rollout, irlmx_demo_statistics, irlmx_demo_log_likelihood: every validation path
     expect(run_roll(nullptr, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "mdp is NULL", "rollout null mdp");
@@ -577,7 +692,7 @@ static void dump_plans() {
                                      {"IRLMX_EXT_GRID_MAX_LAUNCHES", "1000"}};
   const int ops[] = {IRLMX_OP_BACKWARD, IRLMX_OP_FORWARD, IRLMX_OP_SOFT_BACKWARD, IRLMX_OP_VALUE_ITERATION,
                      IRLMX_OP_BACKWARD | IRLMX_PLAN_NO_RESCALE, IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE,
-                     IRLMX_OP_POLICY_EVALUATION};
+                     IRLMX_OP_POLICY_EVALUATION, IRLMX_OP_BACKWARD_HORIZON, IRLMX_OP_FORWARD_HORIZON};
   for (const auto& sw : switches) {
     if (sw[0]) setenv(sw[0], sw[1], 1);
     for_each_model([&](const irlmx_mdp& m, const char* tag) {
@@ -629,6 +744,8 @@ int main(int argc, char** argv) {
   }
   CHECK(g_pe_shapes[0] > 100 && g_pe_shapes[2] > 100, "policy evaluation shapes planned: fused %lld sweep %lld",
         g_pe_shapes[0], g_pe_shapes[2]);
+  CHECK(g_hz_shapes[0] > 200 && g_hz_shapes[2] > 200, "horizon shapes planned: fused %lld sweep %lld", g_hz_shapes[0],
+        g_hz_shapes[2]);
   if (g_fail) {
     fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
     return 1;
