@@ -206,40 +206,24 @@ __global__ void __launch_bounds__(kSweepThreads) ext_final_kernel(ExtArgs a, Ext
 // host-side dispatch
 // ---------------------------------------------------------------------------
 
-// (SPT, KMAX) pairs instantiated: those of the ordinary fused backward; every
-// pair compiles without VGPR spills at __launch_bounds__(1024)
-// (tools/kernel_resources.py).
-static constexpr bool ext_pair_ok(int spt, int kmax) {
-  return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt <= 2) || (kmax == 32 && spt == 1);
-}
-
-template <int S_, int K_>
-static void (*ext_fused_ptr())(ExtArgs) {
-  if constexpr (ext_pair_ok(S_, K_)) return &ext_fused_kernel<S_, K_>;
-  else return nullptr;
-}
-
+// (SPT, KMAX) pairs instantiated: those of the ordinary fused backward
+// (fused_pair_ok); every pair compiles without VGPR spills at
+// __launch_bounds__(1024) (tools/kernel_resources.py).
 static void (*ext_fused_fn(const FusedShape& f))(ExtArgs) {
-  const int s = f.spt, k = f.kmax;
-  if (s == 1 && k == 5) return ext_fused_ptr<1, 5>();
-  if (s == 2 && k == 5) return ext_fused_ptr<2, 5>();
-  if (s == 4 && k == 5) return ext_fused_ptr<4, 5>();
-  if (s == 1 && k == 8) return ext_fused_ptr<1, 8>();
-  if (s == 2 && k == 8) return ext_fused_ptr<2, 8>();
-  if (s == 1 && k == 16) return ext_fused_ptr<1, 16>();
-  if (s == 2 && k == 16) return ext_fused_ptr<2, 16>();
-  if (s == 1 && k == 32) return ext_fused_ptr<1, 32>();
-  return nullptr;
+  return with_pair<void (*)(ExtArgs)>(f.spt, f.kmax, [](auto s, auto k) {
+    if constexpr (fused_pair_ok(IRLMX_OP_BACKWARD, s, k)) return &ext_fused_kernel<s, k>;
+    else return nullptr;
+  });
 }
 
 static size_t ext_fused_lds(const Model& m) { return (size_t)m.S * kExtLdsPerState; }
 
 // The fused shape of the extended pass: the ordinary fused backward's thread
 // layout at every width (there is no cluster form to prefer at 64 / 128), when
-// its registers (an instantiated pair) and LDS fit; else the per-sweep shape.
+// its registers (an instantiated pair: fused_shape asks fused_pair_ok) and LDS
+// fit; else the per-sweep shape.
 static bool ext_fused_shape(const Model& m, FusedShape* out) {
-  if (!fused_shape(m, IRLMX_OP_BACKWARD, out, false)) return false;
-  return ext_pair_ok(out->spt, out->kmax) && ext_fused_lds(m) <= kExtLdsMax;
+  return fused_shape(m, IRLMX_OP_BACKWARD, out, false) && ext_fused_lds(m) <= kExtLdsMax;
 }
 
 // Sequential launches above which a batch goes per sweep instead
@@ -267,7 +251,7 @@ static bool ext_grid_plan(const Model& m, ExtGridPlan* out) {
   if (m.dense || env_int("IRLMX_GRID", 1) == 0) return false;
   if (m.S < env_int("IRLMX_EXT_GRID_MIN_STATES", kExtGridMinStates)) return false;
   if (m.A > kMaxActions || 2LL * m.S + 1 > 0xFFFFFLL) return false;  // sweep tags: 20 bits
-  const int kmax = m.K <= 5 ? 5 : (m.K <= 8 ? 8 : (m.K <= 16 ? 16 : 0));
+  const int kmax = slot_class(m.K, 16);
   if (!kmax) return false;
   const int max_launches = env_int("IRLMX_EXT_GRID_MAX_LAUNCHES", kExtGridMaxLaunches);
   const int forced_cus = env_int("IRLMX_PLAN_CUS", 0);
@@ -297,31 +281,25 @@ static bool ext_grid_plan(const Model& m, ExtGridPlan* out) {
 
 static ExtWs ext_carve(const Model& m, void* base, ExtGridWs* grid = nullptr) {
   ExtWs w;
-  size_t off = 0;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align256(bytes);
-    return (void*)r;
-  };
+  Carver c{(char*)base};
   const size_t B = m.B, S = m.S;
   FusedShape fs;
   const bool sweep = !ext_fused_shape(m, &fs);
-  w.wgt = (double*)take(B * m.K * S * sizeof(double));
-  w.bad = (int32_t*)take(B * sizeof(int32_t));
-  for (int i = 0; i < 2; ++i) w.man[i] = (double*)take(sweep ? B * S * sizeof(double) : 0);
-  for (int i = 0; i < 2; ++i) w.exp[i] = (int32_t*)take(sweep ? B * S * sizeof(int32_t) : 0);
+  w.wgt = c.take<double>(B * m.K * S * sizeof(double));
+  w.bad = c.take<int32_t>(B * sizeof(int32_t));
+  for (int i = 0; i < 2; ++i) w.man[i] = c.take<double>(sweep ? B * S * sizeof(double) : 0);
+  for (int i = 0; i < 2; ++i) w.exp[i] = c.take<int32_t>(sweep ? B * S * sizeof(int32_t) : 0);
   // grid shape: the granules of one launch's instances, beside the per-sweep
   // buffers (which its rerun needs)
   ExtGridPlan gp;
   ExtGridWs g{nullptr, nullptr, nullptr};
   if (sweep && ext_grid_plan(m, &gp)) {
-    g.gran = (unsigned long long*)take((size_t)gp.ipl * 6 * S * 16);
-    g.dgran = (unsigned long long*)take((size_t)gp.ipl * 4 * gp.bpi * 16);
-    g.err = (int*)take(4 * sizeof(int));
+    g.gran = c.take<unsigned long long>((size_t)gp.ipl * 6 * S * 16);
+    g.dgran = c.take<unsigned long long>((size_t)gp.ipl * 4 * gp.bpi * 16);
+    g.err = c.take<int>(4 * sizeof(int));
   }
   if (grid) *grid = g;
-  w.total = off;
+  w.total = c.total();
   return w;
 }
 
@@ -341,14 +319,7 @@ size_t extended_workspace_bytes(const Model& m) { return ext_carve(m, nullptr).t
 
 void extended_plan(const Model& m, int64_t* plan) {
   FusedShape fs;
-  if (ext_fused_shape(m, &fs)) {
-    plan[0] = IRLMX_SHAPE_FUSED;
-    plan[5] = fs.spt;
-    plan[7] = fs.threads;
-    plan[8] = 1;
-    plan[9] = (int64_t)ext_fused_lds(m);
-    return;
-  }
+  if (ext_fused_shape(m, &fs)) return plan_fused(plan, fs, ext_fused_lds(m));
   ExtGridPlan gp;
   if (ext_grid_plan(m, &gp)) {
     plan[0] = IRLMX_SHAPE_GRID;
@@ -360,10 +331,7 @@ void extended_plan(const Model& m, int64_t* plan) {
     plan[8] = gp.launches;
     return;
   }
-  plan[0] = IRLMX_SHAPE_SWEEP;
-  plan[5] = 1;
-  plan[7] = kSweepThreads;
-  plan[8] = 2LL * m.S - 1;  // sweep launches (plus the weights, the start vector and the per-action sweep)
+  plan_sweep(plan, 1, 2LL * m.S - 1);  // sweep launches (plus the weights, the start vector and the per-action sweep)
 }
 
 }  // namespace irlmx
@@ -379,11 +347,8 @@ extern "C" int irlmx_backward_maxent_extended(const irlmx_mdp* mdp, const double
   if (int rc = need_all("backward_maxent_extended",
                         {{reward, "reward"}, {terminal, "terminal"}, {p_action, "p_action"}, {status, "status"}}))
     return rc;
-  const size_t need = ext_carve(m, nullptr).total;
-  if (workspace_bytes < need || !workspace) {
-    set_error("workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    return IRLMX_EWORKSPACE;
-  }
+  // (the need is never 0 -- the weights and flags are always carved -- so a NULL workspace never passes)
+  if (int rc = check_ws(ext_carve(m, nullptr).total, workspace_bytes, workspace)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ExtGridWs gws;
   ExtWs ws = ext_carve(m, workspace, &gws);
@@ -395,19 +360,14 @@ extern "C" int irlmx_backward_maxent_extended(const irlmx_mdp* mdp, const double
   if (ext_fused_shape(m, &fs)) {
     void (*kfn)(ExtArgs) = ext_fused_fn(fs);
     if (!kfn) { set_error("no extended fused kernel for spt=%d kmax=%d", fs.spt, fs.kmax); return IRLMX_EINVAL; }
-    const size_t lds = ext_fused_lds(m);
-    e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-    hipLaunchKernelGGL(kfn, dim3(m.B), dim3(fs.threads), lds, st, a);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "ext_fused_kernel");
+    return launch_fused(kfn, "ext_fused_kernel", m.B, fs.threads, ext_fused_lds(m), st, a);
   }
   ExtGridPlan gp;
   if (gws.gran && ext_grid_plan(m, &gp)) {  // persistent launches; a rendezvous miss reruns the whole call below
     const int rc = ext_grid_run(m, gp, a, gws, st);
     if (rc != kClusterNotResident) return rc;
   }
-  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  const dim3 g = sweep_grid(m);
   count_event(IRLMX_CTR_SWEEP_CALLS);
   hipLaunchKernelGGL(ext_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
   const long long collapsed = 2LL * m.S - 1;

@@ -235,18 +235,16 @@ __global__ void __launch_bounds__(kGridThreads) ext_grid_kernel(ExtArgs a, ExtGr
 }
 
 // (SPT, KMAX) pairs whose gather, 2 * SPT * KMAX + 1 entries, fits gran_gather's
-// 64-bit mask; <2, 16> and <1, 32> stay on the per-sweep shape.  No pair spills
-// VGPRs (tools/kernel_resources.py).
+// 64-bit mask -- the list of the Bellman grid kernels (grid.hip); <2, 16> and
+// <1, 32> stay on the per-sweep shape.  No pair spills VGPRs
+// (tools/kernel_resources.py).
+constexpr bool ext_grid_pair_ok(int spt, int kmax) { return 2 * spt * kmax + 1 <= 64; }
+
 void* ext_grid_fn(int spt, int kmax) {
-  switch (kmax * 8 + spt) {
-    case 5 * 8 + 1: return (void*)&ext_grid_kernel<1, 5>;
-    case 5 * 8 + 2: return (void*)&ext_grid_kernel<2, 5>;
-    case 5 * 8 + 4: return (void*)&ext_grid_kernel<4, 5>;
-    case 8 * 8 + 1: return (void*)&ext_grid_kernel<1, 8>;
-    case 8 * 8 + 2: return (void*)&ext_grid_kernel<2, 8>;
-    case 16 * 8 + 1: return (void*)&ext_grid_kernel<1, 16>;
-  }
-  return nullptr;
+  return with_pair<void*>(spt, kmax, [](auto s, auto k) {
+    if constexpr (ext_grid_pair_ok(s, k)) return (void*)&ext_grid_kernel<s, k>;
+    else return nullptr;
+  });
 }
 
 static std::atomic<unsigned> g_ext_grid_salt{1};

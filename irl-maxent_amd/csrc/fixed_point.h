@@ -1,14 +1,18 @@
-// Model views, the workspace, the stopping-rule helpers, the argument struct
-// of the Bellman kernels and the host helpers of the fixed-point passes that
-// more than one translation unit uses (fixed_point.hip defines the host
-// functions; grid.hip, numpy_order.hip, extended.hip, policy_eval.hip and
-// horizon.hip are the other users).
+// Model views, the workspace and its carver, the stopping-rule helpers, the
+// argument struct of the Bellman kernels and the host plumbing of the
+// fixed-point passes that more than one translation unit uses: the argument and
+// workspace checks, the fused shape with its (SPT, KMAX) predicate, dispatcher
+// (with_pair) and launcher (launch_fused), the slot classes, the per-sweep
+// launch grid and the plan rows (fixed_point.hip defines what is not a
+// template; grid.hip, extended_grid.hip, numpy_order.hip, extended.hip,
+// policy_eval.hip and horizon.hip are the other users).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <initializer_list>
+#include <type_traits>
 
 #include "common.h"
 
@@ -101,9 +105,24 @@ struct Ws {
   size_t total;
 };
 
+// Consecutive 256-byte aligned pieces of a workspace at `base` (nullptr: sizes only).
+struct Carver {
+  char* base;
+  size_t off = 0;
+  template <class T>
+  T* take(size_t bytes) {
+    T* r = base ? (T*)(base + off) : nullptr;
+    off += align256(bytes);
+    return r;
+  }
+  size_t total() const { return off; }
+};
+
 // The workspace of `op` (IRLMX_OP_*) on this model, carved from `base` (nullptr: sizes only).
 Ws carve(const Model& m, int op, void* base);
-// IRLMX_EWORKSPACE and the message unless `bytes` at `ws` hold carve(m, op).total.
+// IRLMX_EWORKSPACE and the message unless `bytes` at `ws` hold `need` (of `op`
+// on this model: carve(m, op).total); a NULL `ws` passes only where need is 0.
+int check_ws(size_t need, size_t bytes, void* ws);
 int check_ws(const Model& m, int op, size_t bytes, void* ws);
 
 // Arguments of the soft VI / VI kernels of every shape (fixed_point.hip fused
@@ -284,6 +303,17 @@ struct Arg {
   const char* name;  // nullptr: optional argument
 };
 int need_all(const char* fn, std::initializer_list<Arg> args);
+// The column form an ELL model's forward passes read: 0, or IRLMX_EINVAL and the message.
+int need_col_form(const Model& m);
+
+// Launch grid of the per-sweep kernels: kSweepThreads states per workgroup, one row per instance.
+inline dim3 sweep_grid(const Model& m) { return dim3((m.S + kSweepThreads - 1) / kSweepThreads, m.B); }
+
+// Slots per state a kernel compiles in for a model of K (5 / 8 / 16 / 32); 0 above `cap`.
+constexpr int slot_class(int K, int cap) {
+  const int k = K <= 5 ? 5 : (K <= 8 ? 8 : (K <= 16 ? 16 : (K <= 32 ? 32 : 0)));
+  return k <= cap ? k : 0;
+}
 
 // The fused shape (one workgroup per instance) of `op` on this model: states
 // per thread, compiled slot count and threads; false when it does not apply.
@@ -296,7 +326,8 @@ struct FusedShape {
 };
 bool fused_shape(const Model& m, int op, FusedShape* out, bool cluster_first = true);
 // (SPT, KMAX) pairs instantiated per op -- the one list fused_shape plans from
-// and every kernel-pointer getter instantiates from: every pair listed compiles
+// and every kernel-pointer getter instantiates from (with_pair below; the
+// extended and the horizon backward take IRLMX_OP_BACKWARD's): every pair listed compiles
 // without VGPR spills at __launch_bounds__(1024) (tools/kernel_resources.py);
 // the soft pass carries fp64 exp/log inline and so keeps fewer states per thread.
 constexpr bool fused_pair_ok(int op, int spt, int kmax) {
@@ -317,6 +348,41 @@ constexpr bool fused_pair_ok(int op, int spt, int kmax) {
 // LDS of the ordinary fused kernels: two S-vectors, the convergence slots and
 // run_deferred's block-start snapshot.
 size_t fused_lds(const Model& m);
+
+// f(integral_constant<int, SPT>, integral_constant<int, KMAX>) of the pair
+// (spt, kmax) out of SPT in {1, 2, 4} x KMAX in {5, 8, 16, 32}; a null R for any
+// other pair.  A kernel family's getter is one generic lambda that returns
+// &kernel<SPT, KMAX> where its constexpr predicate admits the pair and nullptr
+// (under `if constexpr`) where not: the predicate is the instantiation list.
+template <class R, class F>
+R with_pair(int spt, int kmax, F&& f) {
+  R r = nullptr;
+  auto at = [&](auto s, auto k) {
+    if (spt == s && kmax == k) r = f(s, k);
+  };
+  auto row = [&](auto k) {
+    at(std::integral_constant<int, 1>{}, k);
+    at(std::integral_constant<int, 2>{}, k);
+    at(std::integral_constant<int, 4>{}, k);
+  };
+  row(std::integral_constant<int, 5>{});
+  row(std::integral_constant<int, 8>{});
+  row(std::integral_constant<int, 16>{});
+  row(std::integral_constant<int, 32>{});
+  return r;
+}
+
+// One workgroup of `threads` per instance with `lds` bytes of dynamic LDS: 0, or
+// hip_fail's code (`name` names the kernel in the launch's error text).
+int launch_fused_kernel(const void* kfn, const char* name, int B, int threads, size_t lds, hipStream_t st, void* args);
+template <class Args>
+int launch_fused(void (*kfn)(Args), const char* name, int B, int threads, size_t lds, hipStream_t st, Args a) {
+  return launch_fused_kernel((const void*)kfn, name, B, threads, lds, st, &a);
+}
+
+// Plan rows (irlmx_execution_plan's columns) of the two shapes every pass has.
+void plan_fused(int64_t* plan, const FusedShape& fs, size_t lds);
+void plan_sweep(int64_t* plan, int states_per_lane, int64_t launches);
 
 // Enqueue bwd_weights_kernel: w[b][k][s] = exp(r[b][s]) * sum_a P[s, target_k(s), a],
 // bad[b] |= 1 where a weight is non-finite (bwd_nonfinite_rule).

@@ -127,7 +127,7 @@ __global__ void bwd_weights_kernel(Model m, const double* __restrict__ reward, d
 }
 
 void bwd_weights_launch(const Model& m, const double* reward, double* w, int32_t* bad, hipStream_t st) {
-  hipLaunchKernelGGL(bwd_weights_kernel, dim3((m.S + 255) / 256, m.B), dim3(256), 0, st, m, reward, w, bad);
+  hipLaunchKernelGGL(bwd_weights_kernel, sweep_grid(m), dim3(kSweepThreads), 0, st, m, reward, w, bad);
 }
 
 // bwd_nonfinite_rule for the cluster shape: NaN policy for flagged instances
@@ -665,14 +665,6 @@ __global__ void fill_kernel(double* p, size_t n, double v) {
 // host-side dispatch
 // ---------------------------------------------------------------------------
 
-static int pick_kmax(int K) {
-  if (K <= 5) return 5;
-  if (K <= 8) return 8;
-  if (K <= 16) return 16;
-  if (K <= 32) return 32;
-  return 0;
-}
-
 bool fused_shape(const Model& m, int op, FusedShape* out, bool cluster_first) {
   if (m.dense || m.S > fused_max_states() || m.A > kMaxActions) return false;
   // Grids of width 64 / 128 run the forward and backward passes on the cluster
@@ -683,7 +675,7 @@ bool fused_shape(const Model& m, int op, FusedShape* out, bool cluster_first) {
       (m.W == 64 || m.W == 128) && env_int("IRLMX_CLUSTER", 1) != 0)
     return false;
   const int K = op == IRLMX_OP_FORWARD ? m.Kc : m.K;
-  const int kmax = pick_kmax(K);
+  const int kmax = slot_class(K, 32);
   if (!kmax) return false;
   int spt = 1;
   while ((m.S + spt - 1) / spt > 1024) spt *= 2;
@@ -698,40 +690,60 @@ bool fused_shape(const Model& m, int op, FusedShape* out, bool cluster_first) {
 // two S-vectors, the convergence slots and (run_deferred) the block-start snapshot
 size_t fused_lds(const Model& m) { return 3 * (size_t)m.S * sizeof(double) + 4 * sizeof(unsigned long long); }
 
-// Kernel-pointer getters: only the (SPT, KMAX) pairs fused_pair_ok() admits
-// are instantiated.
-#define IRLMX_FUSED_GETTER(NAME, KERNEL_T, OP, ARGS_T)                    \
-  template <int S_, int K_>                                               \
-  static void (*NAME())(ARGS_T) {                                         \
-    if constexpr (fused_pair_ok(OP, S_, K_)) return &KERNEL_T<S_, K_>;    \
-    else return nullptr;                                                  \
-  }
-IRLMX_FUSED_GETTER(fwd_fused_ptr, fwd_fused_kernel, IRLMX_OP_FORWARD, FwdArgs)
-IRLMX_FUSED_GETTER(bwd_fused_ptr, bwd_fused_kernel, IRLMX_OP_BACKWARD, BwdArgs)
-IRLMX_FUSED_GETTER(soft_fused_ptr, soft_fused_kernel, IRLMX_OP_SOFT_BACKWARD, SoftArgs)
-IRLMX_FUSED_GETTER(vi_fused_ptr, vi_fused_kernel, IRLMX_OP_VALUE_ITERATION, SoftArgs)
+// Kernel-pointer getters: fused_pair_ok() is each one's instantiation list (with_pair).
+static void (*fwd_fused_fn(const FusedShape& f))(FwdArgs) {
+  return with_pair<void (*)(FwdArgs)>(f.spt, f.kmax, [](auto s, auto k) {
+    if constexpr (fused_pair_ok(IRLMX_OP_FORWARD, s, k)) return &fwd_fused_kernel<s, k>;
+    else return nullptr;
+  });
+}
+static void (*bwd_fused_fn(const FusedShape& f))(BwdArgs) {
+  return with_pair<void (*)(BwdArgs)>(f.spt, f.kmax, [](auto s, auto k) {
+    if constexpr (fused_pair_ok(IRLMX_OP_BACKWARD, s, k)) return &bwd_fused_kernel<s, k>;
+    else return nullptr;
+  });
+}
+static void (*bellman_fused_fn(bool soft, const FusedShape& f))(SoftArgs) {
+  if (soft)
+    return with_pair<void (*)(SoftArgs)>(f.spt, f.kmax, [](auto s, auto k) {
+      if constexpr (fused_pair_ok(IRLMX_OP_SOFT_BACKWARD, s, k)) return &soft_fused_kernel<s, k>;
+      else return nullptr;
+    });
+  return with_pair<void (*)(SoftArgs)>(f.spt, f.kmax, [](auto s, auto k) {
+    if constexpr (fused_pair_ok(IRLMX_OP_VALUE_ITERATION, s, k)) return &vi_fused_kernel<s, k>;
+    else return nullptr;
+  });
+}
 
-#define IRLMX_DISPATCH_FUSED(GETTER, SHAPE, B, LDS, STREAM, ARGS)                                   \
-  do {                                                                                                \
-    void (*kfn)(decltype(ARGS)) = nullptr;                                                           \
-    const int _s = (SHAPE).spt, _k = (SHAPE).kmax;                                                    \
-    if (_s == 1 && _k == 5) kfn = GETTER<1, 5>();                                                     \
-    else if (_s == 2 && _k == 5) kfn = GETTER<2, 5>();                                                \
-    else if (_s == 4 && _k == 5) kfn = GETTER<4, 5>();                                                \
-    else if (_s == 1 && _k == 8) kfn = GETTER<1, 8>();                                                \
-    else if (_s == 2 && _k == 8) kfn = GETTER<2, 8>();                                                \
-    else if (_s == 4 && _k == 8) kfn = GETTER<4, 8>();                                                \
-    else if (_s == 1 && _k == 16) kfn = GETTER<1, 16>();                                              \
-    else if (_s == 2 && _k == 16) kfn = GETTER<2, 16>();                                              \
-    else if (_s == 1 && _k == 32) kfn = GETTER<1, 32>();                                              \
-    if (!kfn) { set_error("no fused kernel for spt=%d kmax=%d", _s, _k); return IRLMX_EINVAL; }       \
-    hipError_t _e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)(LDS));                                                  \
-    if (_e != hipSuccess) return hip_fail(_e, "hipFuncSetAttribute");                                \
-    hipLaunchKernelGGL(kfn, dim3(B), dim3((SHAPE).threads), (LDS), (STREAM), ARGS);                   \
-    _e = hipGetLastError();                                                                           \
-    if (_e != hipSuccess) return hip_fail(_e, #GETTER);                                               \
-  } while (0)
+// The fused shape's launch of an ordinary pass (`name` names it in a launch error).
+template <class Args>
+static int run_fused(void (*kfn)(Args), const char* name, const Model& m, const FusedShape& f, hipStream_t st,
+                     const Args& a) {
+  if (!kfn) { set_error("no fused kernel for spt=%d kmax=%d", f.spt, f.kmax); return IRLMX_EINVAL; }
+  return launch_fused(kfn, name, m.B, f.threads, fused_lds(m), st, a);
+}
+
+int launch_fused_kernel(const void* kfn, const char* name, int B, int threads, size_t lds, hipStream_t st, void* args) {
+  if (hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return hip_fail(e, "hipFuncSetAttribute");
+  (void)hipLaunchKernel(kfn, dim3(B), dim3(threads), &args, lds, st);  // `args`: the kernel's one parameter
+  const hipError_t e = hipGetLastError();  // this launch's, or an earlier unchecked one's of the same call
+  return e == hipSuccess ? 0 : hip_fail(e, name);
+}
+
+void plan_fused(int64_t* plan, const FusedShape& fs, size_t lds) {
+  plan[0] = IRLMX_SHAPE_FUSED;
+  plan[5] = fs.spt;
+  plan[7] = fs.threads;
+  plan[8] = 1;
+  plan[9] = (int64_t)lds;
+}
+
+void plan_sweep(int64_t* plan, int states_per_lane, int64_t launches) {
+  plan[0] = IRLMX_SHAPE_SWEEP;
+  plan[5] = states_per_lane;
+  plan[7] = kSweepThreads;
+  plan[8] = launches;
+}
 
 int validate(const irlmx_mdp* mdp) {
   if (!mdp) { set_error("mdp is NULL"); return IRLMX_EINVAL; }
@@ -766,14 +778,22 @@ int need_all(const char* fn, std::initializer_list<Arg> args) {
   return 0;
 }
 
-int check_ws(const Model& m, int op, size_t bytes, void* ws) {
-  const size_t need = carve(m, op, nullptr).total;
+int need_col_form(const Model& m) {
+  if (m.stencil || m.dense) return 0;
+  if (!m.col_idx || !m.col_val || m.Kc <= 0) { set_error("ELL column form missing"); return IRLMX_EINVAL; }
+  if (m.Kc > m.S) { set_error("ELL k_col=%d out of range (1..%d)", m.Kc, m.S); return IRLMX_EINVAL; }
+  return 0;
+}
+
+int check_ws(size_t need, size_t bytes, void* ws) {
   if (bytes < need || (need && !ws)) {
     set_error("workspace too small: need %zu bytes, got %zu", need, bytes);
     return IRLMX_EWORKSPACE;
   }
   return 0;
 }
+
+int check_ws(const Model& m, int op, size_t bytes, void* ws) { return check_ws(carve(m, op, nullptr).total, bytes, ws); }
 
 // ---------------------------------------------------------------------------
 // dense-row path (dense.hip)
@@ -856,13 +876,7 @@ static Route route(const Model& m, int op, bool rescale, const std::function<boo
 // The workspace: sized from the route.
 Ws carve(const Model& m, int op, void* base) {
   Ws w;
-  size_t off = 0;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align256(bytes);
-    return (void*)r;
-  };
+  Carver c{(char*)base};
   const size_t B = m.B, S = m.S;
   size_t nw = 0;
   if (op == IRLMX_OP_FORWARD) nw = B * m.Kc * S;  // dense: the per-instance gather matrices WT [B][S][S]
@@ -870,16 +884,16 @@ Ws carve(const Model& m, int op, void* base) {
   if (op == IRLMX_OP_POLICY_EVALUATION) nw = B * m.K * S;           // policy-folded (policy_eval.hip)
   if ((op == IRLMX_OP_SOFT_BACKWARD || op == IRLMX_OP_VALUE_ITERATION) && m.dense && m.shared)
     nw = (size_t)m.A * B * S;  // the per-action GEMM products of a shared dense table
-  w.wgt = (double*)take(nw * sizeof(double));
-  w.bad = (int32_t*)take(B * sizeof(int32_t));
+  w.wgt = c.take<double>(nw * sizeof(double));
+  w.bad = c.take<int32_t>(B * sizeof(int32_t));
   const Route r = route(m, op, false, nullptr, false);
   const bool sweep = r.shape != IRLMX_SHAPE_FUSED;
-  w.buf0 = (double*)take(sweep ? B * S * sizeof(double) : 0);
-  w.buf1 = (double*)take(sweep ? B * S * sizeof(double) : 0);
-  w.slots = (unsigned long long*)take(B * 3 * sizeof(unsigned long long));
-  w.done = (int32_t*)take(B * sizeof(int32_t));
-  w.iters = (int64_t*)take(B * sizeof(int64_t));
-  w.ndone = (int32_t*)take(sizeof(int32_t) * 4);
+  w.buf0 = c.take<double>(sweep ? B * S * sizeof(double) : 0);
+  w.buf1 = c.take<double>(sweep ? B * S * sizeof(double) : 0);
+  w.slots = c.take<unsigned long long>(B * 3 * sizeof(unsigned long long));
+  w.done = c.take<int32_t>(B * sizeof(int32_t));
+  w.iters = c.take<int64_t>(B * sizeof(int64_t));
+  w.ndone = c.take<int32_t>(sizeof(int32_t) * 4);
   // The cluster granules go to every stencil forward and backward that is not
   // fused, a wider rule than the route's: a workspace is sized per model and
   // op, before a backward call says whether it rescales.
@@ -889,12 +903,12 @@ Ws carve(const Model& m, int op, void* base) {
   // grid shape: [B][3][S] value and [B][3][bpi] block-delta granules;
   // dense grid shape: [B][2][S] value and [B][bpi] XCC-id granules
   const size_t gcl = cl ? B * gran_inst_len(m.W, m.H) * 16 : 0;   // cluster.h kGranRowPad layout
-  w.gran = (unsigned long long*)take(std::max(gcl, dg ? 2 * B * S * 16 : (gr ? 3 * B * S * 16 : 0)));
-  w.sgran = (unsigned long long*)take(cl ? kSumRows * B * (size_t)m.H * 16
-                                         : (gr ? 4 * B * (size_t)r.grid.bpi * 16 : (dg ? B * (size_t)r.dense.bpi * 16 : 0)));
-  w.growth = (unsigned long long*)take(cl ? 2 * B * sizeof(unsigned long long) : 0);
-  w.err = (int*)take(cl || gr || dg ? 4 * sizeof(int) : 0);
-  w.total = off;
+  w.gran = c.take<unsigned long long>(std::max(gcl, dg ? 2 * B * S * 16 : (gr ? 3 * B * S * 16 : 0)));
+  w.sgran = c.take<unsigned long long>(cl ? kSumRows * B * (size_t)m.H * 16
+                                          : (gr ? 4 * B * (size_t)r.grid.bpi * 16 : (dg ? B * (size_t)r.dense.bpi * 16 : 0)));
+  w.growth = c.take<unsigned long long>(cl ? 2 * B * sizeof(unsigned long long) : 0);
+  w.err = c.take<int>(cl || gr || dg ? 4 * sizeof(int) : 0);
+  w.total = c.total();
   return w;
 }
 
@@ -1038,7 +1052,7 @@ extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* p
   plan[0] = r.shape;
   switch (r.shape) {
     case IRLMX_SHAPE_FUSED:
-      plan[5] = r.fused.spt; plan[7] = r.fused.threads; plan[8] = 1; plan[9] = (int64_t)fused_lds(m);
+      plan_fused(plan, r.fused, fused_lds(m));
       break;
     case IRLMX_SHAPE_CLUSTER: {
       const ClusterPlan& cp = r.cluster;
@@ -1062,9 +1076,8 @@ extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* p
       plan[7] = kDenseThreads;
       plan[9] = dense_lds_vec(dense_view(m)) ? (int64_t)m.S * 8 : 0;
       break;
-    case IRLMX_SHAPE_SWEEP:
-      plan[7] = kSweepThreads;
-      if (op == IRLMX_OP_POLICY_EVALUATION) plan[5] = 1;  // one state per lane; the launch count is the sweep count
+    case IRLMX_SHAPE_SWEEP:  // (policy evaluation: one state per lane; the launch count is the sweep count)
+      plan_sweep(plan, op == IRLMX_OP_POLICY_EVALUATION ? 1 : 0, 0);
       break;
   }
   return 0;
@@ -1076,8 +1089,7 @@ extern "C" int irlmx_forward_svf(const irlmx_mdp* mdp, const double* p_initial, 
                                  size_t workspace_bytes, void* stream) {
   if (int rc = validate(mdp)) return rc;
   const Model m = make_model(mdp);
-  if (!m.stencil && !m.dense && (!m.col_idx || !m.col_val || m.Kc <= 0)) { set_error("ELL column form missing"); return IRLMX_EINVAL; }
-  if (!m.stencil && !m.dense && m.Kc > m.S) { set_error("ELL k_col=%d out of range (1..%d)", m.Kc, m.S); return IRLMX_EINVAL; }
+  if (int rc = need_col_form(m)) return rc;
   if (int rc = need_all("forward_svf", {{p_initial, "p_initial"}, {terminal, "terminal"}, {p_action, "p_action"},
                                         {svf, "svf"}, {iterations, "iterations"}, {status, "status"}}))
     return rc;
@@ -1086,8 +1098,8 @@ extern "C" int irlmx_forward_svf(const irlmx_mdp* mdp, const double* p_initial, 
   Ws ws = carve(m, IRLMX_OP_FORWARD, workspace);
   hipError_t e = hipMemsetAsync(workspace, 0, ws.total, st);
   if (e != hipSuccess) return hip_fail(e, "workspace memset");
-  const dim3 g((m.S + 255) / 256, m.B);
-  if (!m.dense) hipLaunchKernelGGL(fwd_weights_kernel, g, dim3(256), 0, st, m, p_action, terminal, ws.wgt, ws.bad);
+  const dim3 g = sweep_grid(m);
+  if (!m.dense) hipLaunchKernelGGL(fwd_weights_kernel, g, dim3(kSweepThreads), 0, st, m, p_action, terminal, ws.wgt, ws.bad);
   FwdArgs a{m, ws.wgt, ws.bad, p_initial, eps, (long long)max_iter, svf, iterations, status};
   // dense rows (dense.hip): per-instance gather matrices WT
   const DenseView d = dense_view(m);
@@ -1096,8 +1108,7 @@ extern "C" int irlmx_forward_svf(const irlmx_mdp* mdp, const double* p_initial, 
   const Route r = route(m, IRLMX_OP_FORWARD, true, nullptr);
   switch (r.shape) {
     case IRLMX_SHAPE_FUSED:
-      IRLMX_DISPATCH_FUSED(fwd_fused_ptr, r.fused, m.B, fused_lds(m), st, a);
-      return 0;
+      return run_fused(fwd_fused_fn(r.fused), "fwd_fused_ptr", m, r.fused, st, a);
     case IRLMX_SHAPE_DENSE_GRID: {  // one persistent launch, WT's rows in registers
       DenseGridArgs ga = dense_grid_args(m, ws);
       ga.mat = ws.wgt; ga.vin = p_initial; ga.bad = ws.bad; ga.eps = eps; ga.max_iter = (long long)max_iter;
@@ -1122,7 +1133,7 @@ extern "C" int irlmx_forward_svf(const irlmx_mdp* mdp, const double* p_initial, 
       if (rc == kClusterNonFinite) count_event(IRLMX_CTR_RERUN_NONFINITE);
       e = hipMemsetAsync(workspace, 0, ws.total, st);
       if (e != hipSuccess) return hip_fail(e, "workspace memset");
-      hipLaunchKernelGGL(fwd_weights_kernel, g, dim3(256), 0, st, m, p_action, terminal, ws.wgt, ws.bad);
+      hipLaunchKernelGGL(fwd_weights_kernel, g, dim3(kSweepThreads), 0, st, m, p_action, terminal, ws.wgt, ws.bad);
       break;
     }
     case IRLMX_SHAPE_GRID: {  // ELL models: one persistent launch
@@ -1135,14 +1146,13 @@ extern "C" int irlmx_forward_svf(const irlmx_mdp* mdp, const double* p_initial, 
     }
   }
   // the per-sweep shape: the route's choice, or the rerun of a persistent launch
-  const dim3 gs((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
   count_event(IRLMX_CTR_SWEEP_CALLS);
   int rc = run_until_done(ws, m.B, st, [&](long long it, int r3) {
     if (m.dense) dense_fwd_sweep_launch(d, p_initial, eps, (long long)max_iter, status, w, it, r3, st);
-    else hipLaunchKernelGGL(fwd_sweep_kernel, gs, dim3(kSweepThreads), 0, st, a, ws, it, r3);
+    else hipLaunchKernelGGL(fwd_sweep_kernel, g, dim3(kSweepThreads), 0, st, a, ws, it, r3);
   });
   if (rc) return rc;
-  hipLaunchKernelGGL(fwd_finish_kernel, g, dim3(256), 0, st, a, ws);
+  hipLaunchKernelGGL(fwd_finish_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
   e = hipGetLastError();
   return e == hipSuccess ? 0 : hip_fail(e, m.dense ? "dense forward" : "fwd_finish");
 }
@@ -1166,8 +1176,7 @@ extern "C" int irlmx_backward_maxent(const irlmx_mdp* mdp, const double* reward,
   BwdArgs a{m, ws.wgt, reward, terminal, rescale, p_action, status};
   switch (r.shape) {
     case IRLMX_SHAPE_FUSED:
-      IRLMX_DISPATCH_FUSED(bwd_fused_ptr, r.fused, m.B, fused_lds(m), st, a);
-      return 0;
+      return run_fused(bwd_fused_fn(r.fused), "bwd_fused_ptr", m, r.fused, st, a);
     case IRLMX_SHAPE_CLUSTER: {
       hipLaunchKernelGGL(bwd_growth_kernel, dim3(m.B), dim3(1024), 0, st, ws.wgt, m.W, m.S, m.B, ws.growth);
       ClusterArgs ca{};
@@ -1203,7 +1212,7 @@ extern "C" int irlmx_backward_maxent(const irlmx_mdp* mdp, const double* reward,
     }
   }
   // the per-sweep shape: the route's choice, or the rerun of a persistent launch
-  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  const dim3 g = sweep_grid(m);
   count_event(IRLMX_CTR_SWEEP_CALLS);
   hipLaunchKernelGGL(bwd_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
   const long long collapsed = 2LL * m.S - 1;
@@ -1261,11 +1270,8 @@ static int bellman_common(const irlmx_mdp* mdp, const double* reward, const doub
   if (e != hipSuccess) return hip_fail(e, "workspace memset");
   SoftArgs a{m, reward, phi, discount, eps, (long long)max_iter, average, p_action, value, iterations, status};
   const Route r = route(m, op, true, nullptr);
-  if (r.shape == IRLMX_SHAPE_FUSED) {
-    if (soft) IRLMX_DISPATCH_FUSED(soft_fused_ptr, r.fused, m.B, fused_lds(m), st, a);
-    else IRLMX_DISPATCH_FUSED(vi_fused_ptr, r.fused, m.B, fused_lds(m), st, a);
-    return 0;
-  }
+  if (r.shape == IRLMX_SHAPE_FUSED)
+    return run_fused(bellman_fused_fn(soft, r.fused), soft ? "soft_fused_ptr" : "vi_fused_ptr", m, r.fused, st, a);
   const size_t n = (size_t)m.B * m.S;
   hipLaunchKernelGGL(fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ws.buf0, n, soft ? -1e200 : 0.0);
   if (r.shape == IRLMX_SHAPE_DENSE_GRID) {  // one persistent launch, the A rows of each state in registers
@@ -1287,7 +1293,7 @@ static int bellman_common(const irlmx_mdp* mdp, const double* reward, const doub
                         iterations, status};
   const bool gemm = r.shape == IRLMX_SHAPE_DENSE_GEMM;  // the P . [v_1 .. v_B] products on the MFMA kernel
   hipError_t gerr = hipSuccess;
-  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  const dim3 g = sweep_grid(m);
   // the Bellman sweep is a latency chain per state (A dots, A softmax folds):
   // smaller workgroups spread one instance over more CUs (IRLMX_BELLMAN_THREADS)
   const int bt = std::max(64, std::min(kSweepThreads, env_int("IRLMX_BELLMAN_THREADS", kSweepThreads)));

@@ -444,38 +444,38 @@ __global__ void __launch_bounds__(kGridThreads) linear_grid_kernel(LinearGridArg
   }
 }
 
-// NAME<T>(spt, kmax): the <T, SPT, KMAX> instantiation of a grid kernel, nullptr
-// for a pair that is not compiled.  WIDE: also <2, 16> and <1, 32>.
-#define IRLMX_GRID_FN(NAME, KERNEL, TPARAM, WIDE)                              \
-  template <TPARAM T>                                                          \
-  static void* NAME(int spt, int kmax) {                                       \
-    switch (kmax * 8 + spt) {                                                  \
-      case 5 * 8 + 1: return (void*)&KERNEL<T, 1, 5>;                          \
-      case 5 * 8 + 2: return (void*)&KERNEL<T, 2, 5>;                          \
-      case 5 * 8 + 4: return (void*)&KERNEL<T, 4, 5>;                          \
-      case 8 * 8 + 1: return (void*)&KERNEL<T, 1, 8>;                          \
-      case 8 * 8 + 2: return (void*)&KERNEL<T, 2, 8>;                          \
-      case 16 * 8 + 1: return (void*)&KERNEL<T, 1, 16>;                        \
-    }                                                                          \
-    if constexpr (WIDE) {                                                      \
-      if (kmax == 16 && spt == 2) return (void*)&KERNEL<T, 2, 16>;             \
-      if (kmax == 32 && spt == 1) return (void*)&KERNEL<T, 1, 32>;             \
-    }                                                                          \
-    return nullptr;                                                            \
-  }
-IRLMX_GRID_FN(bellman_grid_fn, bellman_grid_kernel, bool, false)
-IRLMX_GRID_FN(linear_grid_fn, linear_grid_kernel, int, true)
-
-// slots per state the grid kernels hold in registers: the linear loops up to 32
-// (ELL rows / columns of generic sparse models), the Bellman loops up to 16
-// (their A x K weights)
-static int grid_kmax_of(int K, int cap) {
-  const int k = K <= 5 ? 5 : (K <= 8 ? 8 : (K <= 16 ? 16 : (K <= 32 ? 32 : 0)));
-  return k <= cap ? k : 0;
+// (SPT, KMAX) pairs instantiated.  The Bellman loops hold A x K weights per
+// state: up to 16 slots, fewer states per thread as the slots grow.  The linear
+// loops hold one weight per slot (ELL rows / columns of generic sparse models):
+// also <2, 16> and <1, 32>.
+constexpr bool bellman_grid_pair_ok(int spt, int kmax) {
+  return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt == 1);
 }
-static int grid_kmax(const Model& m) { return grid_kmax_of(m.K, 16); }
-static int grid_kmax_lin(const Model& m) { return grid_kmax_of(m.K, 32); }
-static int grid_kmax_fwd(const Model& m) { return grid_kmax_of(m.Kc, 32); }
+constexpr bool linear_grid_pair_ok(int spt, int kmax) {
+  return bellman_grid_pair_ok(spt, kmax) || (kmax == 16 && spt == 2) || (kmax == 32 && spt == 1);
+}
+
+// The <T, SPT, KMAX> instantiation of a grid kernel, nullptr for a pair that is not compiled.
+template <bool SOFT>
+static void* bellman_grid_fn(int spt, int kmax) {
+  return with_pair<void*>(spt, kmax, [](auto s, auto k) {
+    if constexpr (bellman_grid_pair_ok(s, k)) return (void*)&bellman_grid_kernel<SOFT, s, k>;
+    else return nullptr;
+  });
+}
+template <int MODE>
+static void* linear_grid_fn(int spt, int kmax) {
+  return with_pair<void*>(spt, kmax, [](auto s, auto k) {
+    if constexpr (linear_grid_pair_ok(s, k)) return (void*)&linear_grid_kernel<MODE, s, k>;
+    else return nullptr;
+  });
+}
+
+// slots per state the grid kernels hold in registers (slot_class): the linear
+// loops up to 32, the Bellman loops up to 16
+static int grid_kmax(const Model& m) { return slot_class(m.K, 16); }
+static int grid_kmax_lin(const Model& m) { return slot_class(m.K, 32); }
+static int grid_kmax_fwd(const Model& m) { return slot_class(m.Kc, 32); }
 
 static void* grid_fn(const Model& m, int op, int spt) {
   switch (op) {

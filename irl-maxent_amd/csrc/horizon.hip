@@ -443,32 +443,20 @@ __global__ void __launch_bounds__(kSweepThreads) hz_fwd_step_kernel(HzFwdArgs a,
 // host-side dispatch
 // ---------------------------------------------------------------------------
 
-// (SPT, KMAX) pairs of the backward: the extended backward's list; every pair
-// compiles without VGPR spills at __launch_bounds__(1024)
-// (tools/kernel_resources.py; the table is in DESIGN.md section 4).
-static constexpr bool hz_pair_ok(int spt, int kmax) {
-  return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt <= 2) || (kmax == 32 && spt == 1);
-}
 // Pairs whose table values stay in registers (at most kHzRegActions actions).
 static constexpr bool hz_pair_reg(int spt, int kmax) { return spt == 1 && kmax == 5; }
 
-template <int S_, int K_, bool R_>
-static void (*hz_bwd_ptr())(HzBwdArgs) {
-  if constexpr (hz_pair_ok(S_, K_) && (!R_ || hz_pair_reg(S_, K_))) return &hz_bwd_fused_kernel<S_, K_, R_>;
-  else return nullptr;
-}
-
+// (SPT, KMAX) pairs of the backward: the ordinary fused backward's list
+// (fused_pair_ok), as the extended backward; every pair compiles without VGPR
+// spills at __launch_bounds__(1024) (tools/kernel_resources.py; the table is in
+// DESIGN.md section 4).
 template <bool R_>
-static void (*hz_bwd_fn(int s, int k))(HzBwdArgs) {
-  if (s == 1 && k == 5) return hz_bwd_ptr<1, 5, R_>();
-  if (s == 2 && k == 5) return hz_bwd_ptr<2, 5, R_>();
-  if (s == 4 && k == 5) return hz_bwd_ptr<4, 5, R_>();
-  if (s == 1 && k == 8) return hz_bwd_ptr<1, 8, R_>();
-  if (s == 2 && k == 8) return hz_bwd_ptr<2, 8, R_>();
-  if (s == 1 && k == 16) return hz_bwd_ptr<1, 16, R_>();
-  if (s == 2 && k == 16) return hz_bwd_ptr<2, 16, R_>();
-  if (s == 1 && k == 32) return hz_bwd_ptr<1, 32, R_>();
-  return nullptr;
+static void (*hz_bwd_fn(int spt, int kmax))(HzBwdArgs) {
+  return with_pair<void (*)(HzBwdArgs)>(spt, kmax, [](auto s, auto k) {
+    if constexpr (fused_pair_ok(IRLMX_OP_BACKWARD, s, k) && (!R_ || hz_pair_reg(s, k)))
+      return &hz_bwd_fused_kernel<s, k, R_>;
+    else return nullptr;
+  });
 }
 
 static void (*hz_fwd_fn(int spt))(HzFwdArgs) {
@@ -484,8 +472,9 @@ static size_t hz_fused_lds(const Model& m, int op) {
 
 // The fused shape of a horizon pass: the thread layout of the ordinary fused
 // backward / forward at every width (these passes have no cluster form), when
-// its pair is instantiated, its LDS fits and (several states per thread) the
-// batch is large enough; else one launch per step.
+// its pair is instantiated (fused_shape asks fused_pair_ok; the forward has no
+// slot classes), its LDS fits and (several states per thread) the batch is
+// large enough; else one launch per step.
 // Several states per thread (above 1,024 states) only from this many instances
 // on (IRLMX_HORIZON_FUSED_BATCH; tests use 1): one workgroup steps 4,096 states
 // in 24 us where a launch over 16 workgroups takes 11, so below one workgroup
@@ -501,28 +490,21 @@ static int hz_fused_min_batch() {
 static bool hz_fused_shape(const Model& m, int op, FusedShape* out) {
   const bool bwd = op == IRLMX_OP_BACKWARD_HORIZON;
   if (!fused_shape(m, bwd ? IRLMX_OP_BACKWARD : IRLMX_OP_FORWARD, out, false)) return false;
-  if (bwd && !hz_pair_ok(out->spt, out->kmax)) return false;
   if (out->spt > 1 && m.B < hz_fused_min_batch()) return false;
   return hz_fused_lds(m, op) <= kExtLdsMax;
 }
 
 static HzWs hz_carve(const Model& m, int op, void* base) {
   HzWs w;
-  size_t off = 0;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align256(bytes);
-    return (void*)r;
-  };
+  Carver c{(char*)base};
   const size_t B = m.B, S = m.S;
   FusedShape fs;
   const bool sweep = !hz_fused_shape(m, op, &fs);
   const bool bwd = op == IRLMX_OP_BACKWARD_HORIZON;
-  w.bad = (int32_t*)take(sweep && bwd ? B * sizeof(int32_t) : 0);
-  for (int i = 0; i < 2; ++i) w.man[i] = (double*)take(sweep ? B * S * sizeof(double) : 0);
-  for (int i = 0; i < 2; ++i) w.exp[i] = (int32_t*)take(sweep && bwd ? B * S * sizeof(int32_t) : 0);
-  w.total = off;
+  w.bad = c.take<int32_t>(sweep && bwd ? B * sizeof(int32_t) : 0);
+  for (int i = 0; i < 2; ++i) w.man[i] = c.take<double>(sweep ? B * S * sizeof(double) : 0);
+  for (int i = 0; i < 2; ++i) w.exp[i] = c.take<int32_t>(sweep && bwd ? B * S * sizeof(int32_t) : 0);
+  w.total = c.total();
   return w;
 }
 
@@ -538,17 +520,8 @@ size_t horizon_workspace_bytes(const Model& m, int op) { return hz_carve(m, op, 
 
 void horizon_plan(const Model& m, int op, int64_t* plan) {
   FusedShape fs;
-  if (hz_fused_shape(m, op, &fs)) {
-    plan[0] = IRLMX_SHAPE_FUSED;
-    plan[5] = fs.spt;
-    plan[7] = fs.threads;
-    plan[8] = 1;
-    plan[9] = (int64_t)hz_fused_lds(m, op);
-    return;
-  }
-  plan[0] = IRLMX_SHAPE_SWEEP;
-  plan[5] = 1;  // one state per lane; the launch count is the horizon
-  plan[7] = kSweepThreads;
+  if (hz_fused_shape(m, op, &fs)) return plan_fused(plan, fs, hz_fused_lds(m, op));
+  plan_sweep(plan, 1, 0);  // one state per lane; the launch count is the horizon
 }
 
 static int hz_check_call(const Model& m, const char* fn, int op, int32_t horizon, size_t bytes, void* ws) {
@@ -556,12 +529,7 @@ static int hz_check_call(const Model& m, const char* fn, int op, int32_t horizon
     set_error("%s: horizon %d outside [1, %d]", fn, horizon, kHzMaxHorizon);
     return IRLMX_EINVAL;
   }
-  const size_t need = hz_carve(m, op, nullptr).total;
-  if (bytes < need || (need && !ws)) {
-    set_error("workspace too small: need %zu bytes, got %zu", need, bytes);
-    return IRLMX_EWORKSPACE;
-  }
-  return 0;
+  return check_ws(hz_carve(m, op, nullptr).total, bytes, ws);
 }
 
 }  // namespace irlmx
@@ -585,18 +553,13 @@ extern "C" int irlmx_backward_maxent_horizon(const irlmx_mdp* mdp, const double*
     if (m.A <= kHzRegActions) kfn = hz_bwd_fn<true>(fs.spt, fs.kmax);
     if (!kfn) kfn = hz_bwd_fn<false>(fs.spt, fs.kmax);
     if (!kfn) { set_error("no horizon backward fused kernel for spt=%d kmax=%d", fs.spt, fs.kmax); return IRLMX_EINVAL; }
-    const size_t lds = hz_fused_lds(m, IRLMX_OP_BACKWARD_HORIZON);
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-    hipLaunchKernelGGL(kfn, dim3(m.B), dim3(fs.threads), lds, st, a);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "hz_bwd_fused_kernel");
+    return launch_fused(kfn, "hz_bwd_fused_kernel", m.B, fs.threads, hz_fused_lds(m, IRLMX_OP_BACKWARD_HORIZON), st, a);
   }
   HzWs ws = hz_carve(m, IRLMX_OP_BACKWARD_HORIZON, workspace);
   hipError_t e = hipMemsetAsync(ws.bad, 0, (size_t)m.B * sizeof(int32_t), st);
   if (e != hipSuccess) return hip_fail(e, "workspace memset");
   count_event(IRLMX_CTR_SWEEP_CALLS);
-  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  const dim3 g = sweep_grid(m);
   hipLaunchKernelGGL(hz_bwd_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
   for (int it = 0; it < horizon; ++it)
     hipLaunchKernelGGL(hz_bwd_step_kernel, g, dim3(kSweepThreads), 0, st, a, ws, horizon - 1 - it, it & 1);
@@ -611,10 +574,7 @@ extern "C" int irlmx_forward_svf_horizon(const irlmx_mdp* mdp, const double* p_i
   if (int rc = validate(mdp)) return rc;
   const Model m = make_model(mdp);
   if (int rc = horizon_check_model(m, fn)) return rc;
-  if (!m.stencil && (!m.col_idx || !m.col_val || m.Kc <= 0)) {
-    set_error("ELL column form missing");
-    return IRLMX_EINVAL;
-  }
+  if (int rc = need_col_form(m)) return rc;
   if (int rc = need_all(fn, {{p_initial, "p_initial"}, {p_action_t, "p_action_t"}, {svf, "svf"}, {status, "status"}}))
     return rc;
   if (int rc = hz_check_call(m, fn, IRLMX_OP_FORWARD_HORIZON, horizon, workspace_bytes, workspace)) return rc;
@@ -624,16 +584,11 @@ extern "C" int irlmx_forward_svf_horizon(const irlmx_mdp* mdp, const double* p_i
   if (hz_fused_shape(m, IRLMX_OP_FORWARD_HORIZON, &fs)) {
     void (*kfn)(HzFwdArgs) = hz_fwd_fn(fs.spt);
     if (!kfn) { set_error("no horizon forward fused kernel for spt=%d", fs.spt); return IRLMX_EINVAL; }
-    const size_t lds = hz_fused_lds(m, IRLMX_OP_FORWARD_HORIZON);
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-    hipLaunchKernelGGL(kfn, dim3(m.B), dim3(fs.threads), lds, st, a);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "hz_fwd_fused_kernel");
+    return launch_fused(kfn, "hz_fwd_fused_kernel", m.B, fs.threads, hz_fused_lds(m, IRLMX_OP_FORWARD_HORIZON), st, a);
   }
   HzWs ws = hz_carve(m, IRLMX_OP_FORWARD_HORIZON, workspace);
   count_event(IRLMX_CTR_SWEEP_CALLS);
-  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  const dim3 g = sweep_grid(m);
   hipLaunchKernelGGL(hz_fwd_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
   for (int t = 0; t < horizon; ++t)
     hipLaunchKernelGGL(hz_fwd_step_kernel, g, dim3(kSweepThreads), 0, st, a, ws, t, t & 1);

@@ -826,13 +826,9 @@ static int np_launch(NpKernels<Args>& k, const Model& m, const Args& a, size_t l
                      hipStream_t st) {
   const bool cached = m.stencil && m.S <= kNpCachedMaxStates && m.A <= kNpCachedMaxActions;
   void (*kfn)(Args) = k[cached ? (m.S <= kNpCachedThreads ? 0 : 1) : m.stencil ? 2 : (m.dense ? 3 : 4)];
-  hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
   const int nthr = cached ? std::min(kNpCachedThreads, ((m.S + kWave - 1) / kWave) * kWave)
                           : (m.S >= 1024 ? 1024 : ((m.S + kWave - 1) / kWave) * kWave);
-  hipLaunchKernelGGL(kfn, dim3(m.B), dim3(nthr), lds, st, a);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, fn);
+  return launch_fused(kfn, fn, m.B, nthr, lds, st, a);
 }
 
 template <bool SOFT>

@@ -229,24 +229,11 @@ __global__ void pe_finish_kernel(PeArgs a, Ws ws) {
 // (SPT, KMAX) pairs instantiated: fused_pair_ok's list for this op, the one
 // fused_shape plans from (fixed_point.h); every pair compiles without VGPR
 // spills at __launch_bounds__(1024) (tools/kernel_resources.py).
-template <int S_, int K_>
-static void (*pe_fused_ptr())(PeArgs) {
-  if constexpr (fused_pair_ok(IRLMX_OP_POLICY_EVALUATION, S_, K_)) return &pe_fused_kernel<S_, K_>;
-  else return nullptr;
-}
-
 static void (*pe_fused_fn(const FusedShape& f))(PeArgs) {
-  const int s = f.spt, k = f.kmax;
-  if (s == 1 && k == 5) return pe_fused_ptr<1, 5>();
-  if (s == 2 && k == 5) return pe_fused_ptr<2, 5>();
-  if (s == 4 && k == 5) return pe_fused_ptr<4, 5>();
-  if (s == 1 && k == 8) return pe_fused_ptr<1, 8>();
-  if (s == 2 && k == 8) return pe_fused_ptr<2, 8>();
-  if (s == 4 && k == 8) return pe_fused_ptr<4, 8>();
-  if (s == 1 && k == 16) return pe_fused_ptr<1, 16>();
-  if (s == 2 && k == 16) return pe_fused_ptr<2, 16>();
-  if (s == 1 && k == 32) return pe_fused_ptr<1, 32>();
-  return nullptr;
+  return with_pair<void (*)(PeArgs)>(f.spt, f.kmax, [](auto s, auto k) {
+    if constexpr (fused_pair_ok(IRLMX_OP_POLICY_EVALUATION, s, k)) return &pe_fused_kernel<s, k>;
+    else return nullptr;
+  });
 }
 
 int policy_eval_check_model(const Model& m, const char* fn) {
@@ -278,7 +265,7 @@ extern "C" int irlmx_policy_evaluation(const irlmx_mdp* mdp, const double* rewar
   if (int rc = check_ws(m, IRLMX_OP_POLICY_EVALUATION, workspace_bytes, workspace)) return rc;
   hipStream_t st = (hipStream_t)stream;
   Ws ws = carve(m, IRLMX_OP_POLICY_EVALUATION, workspace);
-  const dim3 g((m.S + kSweepThreads - 1) / kSweepThreads, m.B);
+  const dim3 g = sweep_grid(m);
   hipLaunchKernelGGL(pe_weights_kernel, g, dim3(kSweepThreads), 0, st, m, p_action, terminal, ws.wgt);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "pe_weights_kernel");
@@ -287,12 +274,7 @@ extern "C" int irlmx_policy_evaluation(const irlmx_mdp* mdp, const double* rewar
   if (fused_shape(m, IRLMX_OP_POLICY_EVALUATION, &fs)) {
     void (*kfn)(PeArgs) = pe_fused_fn(fs);
     if (!kfn) { set_error("no policy evaluation fused kernel for spt=%d kmax=%d", fs.spt, fs.kmax); return IRLMX_EINVAL; }
-    const size_t lds = fused_lds(m);
-    e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-    hipLaunchKernelGGL(kfn, dim3(m.B), dim3(fs.threads), lds, st, a);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "pe_fused_kernel");
+    return launch_fused(kfn, "pe_fused_kernel", m.B, fs.threads, fused_lds(m), st, a);
   }
   // the sweep shape's state, everything carved after the weights (which
   // pe_weights_kernel writes in full): v = 0, the ring, the done flags and count;

@@ -99,8 +99,8 @@ GRID = {
     "k40-s300": (_, _, _, _),
 }
 
-# -- the planner, restated (csrc/fixed_point.hip: pick_kmax, fused_pair_ok, fused_shape; csrc/grid.hip: grid_plan;
-#    csrc/extended.hip: ext_pair_ok is the backward's list) ----------------------------------
+# -- the planner, restated (csrc/fixed_point.h: slot_class, fused_pair_ok; csrc/fixed_point.hip: fused_shape;
+#    csrc/grid.hip: grid_plan; csrc/extended.hip takes the backward's list) -------------------
 
 FUSED_MAX_STATES, MAX_ACTIONS, GRID_MAX_ACTIONS, GRID_THREADS, WAVE = 4096, 8, 5, 256, 64
 _LINEAR = {5: (1, 2, 4), 8: (1, 2), 16: (1, 2), 32: (1,)}
@@ -266,7 +266,7 @@ def numpy_order_reward(c):
 def expected_plan(c, op, fused_max=FUSED_MAX_STATES, pad=0):
     """plan() of case c with ``pad`` slots more than needed (the scrambled form).
     ``op="extended"`` (ops.backward_maxent_extended): fused wherever the
-    backward's pair is (ext_pair_ok is the backward's list; 24 B of LDS per state
+    backward's pair is (it takes the backward's list; 24 B of LDS per state
     fit at every size here), else one launch per sweep -- it has no grid form."""
     p = plan(c.S, c.A, c.k_row + pad, c.k_col + pad, "backward" if op == "extended" else op, fused_max)
     return {"shape": "sweep"} if op == "extended" and p["shape"] != "fused" else p

@@ -112,6 +112,9 @@ def test_bad_model(lib):
     assert backward(lib, model(S=0)) == EINVAL and "bad sizes S=0" in err(lib)
     assert backward(lib, model(layout=2, k_row=3)) == EINVAL and err(lib) == "ELL row form missing"
     assert forward(lib, model(layout=2, k_row=3, row_idx=True)) == EINVAL and err(lib) == "ELL column form missing"
+    # more column slots than states: refused as irlmx_forward_svf refuses it (the kernels would index past the column form)
+    wide = model(layout=2, k_row=3, k_col=30, row_idx=True, col=True)
+    assert forward(lib, wide) == EINVAL and err(lib) == "ELL k_col=30 out of range (1..25)", err(lib)
 
 
 def test_dense_layout_refused(lib):

@@ -4,7 +4,7 @@ matrix of kernel instantiations and both slot layouts (needs an MI355X).
 The ELL kernels are compiled per (states per thread, slot class) pair and per
 execution shape; the other suites enter that matrix at a handful of points,
 always with one shared table in irlmx_dense_to_ell's slot layout.  The cases of
-tests/ell_cases.py reach every fused pair fused_pair_ok / ext_pair_ok admit, the
+tests/ell_cases.py reach every fused pair fused_pair_ok admits for each pass, the
 planner's fallbacks (a pair that is not instantiated, k_row or k_col above 32,
 A above the grid shape's 5), A = 1 and A = 8, and the persistent grid shape
 with 8, 16 and 32 slots -- each with B = 2 or 3 different tables in one launch

@@ -505,6 +505,8 @@ static void error_paths() {
     irlmx_mdp nocol = ell(25, 4, 3, 3, 1);
     nocol.col_idx = nullptr;
     expect(run_hzf(&nocol, f, f, f, 8, f, f, f, f, nf), IRLMX_EINVAL, "ELL column form missing", "horizon forward without columns");
+    irlmx_mdp widecol = ell(25, 4, 3, 30, 1);
+    expect(run_hzf(&widecol, f, f, f, 8, f, f, f, f, nf), IRLMX_EINVAL, "ELL k_col=30 out of range (1..25)", "horizon forward k_col > S");
     expect(run_hzb(&big, nullptr, f, 8, f, f, f, f, nb), IRLMX_EINVAL, "backward_maxent_horizon: reward is NULL", "horizon null reward");
     expect(run_hzb(&big, f, f, 8, nullptr, f, f, f, nb), IRLMX_EINVAL, "p_action_t is NULL", "horizon backward null p_action_t");
     expect(run_hzb(&big, f, f, 8, f, f, nullptr, f, nb), IRLMX_EINVAL, "status is NULL", "horizon backward null status");
