@@ -162,7 +162,33 @@ int irlmx_mdp_properties(const irlmx_mdp* mdp, int32_t* props, void* stream);
 #define IRLMX_NPMATH_LOG 1
 int irlmx_numpy_math(int32_t op, const double* x, double* y, int64_t n, void* stream);
 
-/* Bytes of device workspace `op` needs for this model (0 is a valid answer). */
+/*
+ * Bytes of device workspace `op` needs for this model (0 is a valid answer; a
+ * multiple of 256).
+ *
+ * The call contract of every entry point that takes `workspace`,
+ * `workspace_bytes` (tests/test_gpu_call_contract.py holds each of them, on
+ * every execution shape, to all of it):
+ *  - The contents of the workspace on entry are ignored: a call's results do not
+ *    depend on them, so a workspace may come straight from an allocator or from
+ *    an earlier call, of this or any other entry point.  Its contents on return
+ *    are unspecified.
+ *  - A call reads and writes nothing at or beyond workspace + workspace_bytes,
+ *    and nothing before workspace.  workspace_bytes may be larger than the
+ *    need; a need of 0 accepts a NULL workspace.
+ *  - workspace is aligned as hipMalloc and torch's allocator align theirs, to
+ *    256 bytes.  (The library does not check the alignment.)
+ *  - The workspace belongs to the call until the work the call enqueued on
+ *    `stream` has completed.  Two calls in flight at the same time -- on two
+ *    streams, or from two host threads -- must not share one; calls that follow
+ *    each other on one stream may.
+ *  - A call that returns 0 writes every entry of every non-NULL output array:
+ *    all of p_action / svf / value, `status` and `iterations` of every
+ *    instance, the outputs of instances whose status is not IRLMX_OK included
+ *    (an optional output that is given -- value, log_z0, svf_t -- likewise).
+ *    No output entry is read before it is written: outputs may be
+ *    uninitialised memory.
+ */
 size_t irlmx_workspace_bytes(const irlmx_mdp* mdp, int32_t op);
 
 /*

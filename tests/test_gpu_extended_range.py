@@ -82,19 +82,12 @@ def wide_inputs(cases, dev):
 
 
 def run_ext(mdp, reward, term):
-    """(policy, status) through the C ABI (ops.backward_maxent_extended returns the policy alone)."""
-    from irlmx import _lib, ops
-    lib = _lib.load()
-    B, S, A = mdp.batch, mdp.n_states, mdp.n_actions
-    r = torch.as_tensor(np.array(reward, dtype=np.float64), device=mdp.device).reshape(B, S).contiguous()
-    tm = term.to(device=mdp.device, dtype=torch.uint8).reshape(B, S).contiguous()
-    pi = torch.empty((B, S, A), dtype=torch.float64, device=mdp.device)
-    status = torch.full((B,), -7, dtype=torch.int32, device=mdp.device)
-    ws, n = ops._workspace(mdp, _lib.OP_BACKWARD | _lib.PLAN_EXTENDED_RANGE)
-    _lib.check(lib.irlmx_backward_maxent_extended(mdp.struct(), _lib.ptr(r), _lib.ptr(tm), _lib.ptr(pi),
-                                                  _lib.ptr(status), _lib.ptr(ws), n, _lib.stream_ptr(mdp.device)),
-               "backward_maxent_extended")
-    return pi, status.cpu().numpy()
+    """(policy, status) through the C ABI (ops.backward_maxent_extended returns the policy alone): the call
+    of tests/abi_call.py, which also guards the workspace and requires every output entry written (the
+    status is prefilled with -7, the policy with a sentinel NaN)."""
+    import abi_call
+    out = abi_call.backward_maxent_extended(mdp, np.array(reward, dtype=np.float64), term)
+    return out["p_action"], out["status"].cpu().numpy()
 
 
 def assert_fused_plan(mdp):
