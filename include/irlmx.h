@@ -60,6 +60,7 @@ extern "C" {
 #define IRLMX_OP_POLICY_EVALUATION 6 /* 5 stays an unknown op: ABI version 1 has always answered "unknown op 5" */
 #define IRLMX_OP_BACKWARD_HORIZON 8  /* 5 and 7 stay unknown ops: tests and tools/sanitize pin both answers */
 #define IRLMX_OP_FORWARD_HORIZON 9
+#define IRLMX_OP_SOFT_BACKWARD_HORIZON 11 /* 10 stays an unknown op too: the same tests pin "unknown op 10" */
 
 /*
  * Transition model P[from, to, action] of B instances (the reference's dense
@@ -185,7 +186,7 @@ int irlmx_numpy_math(int32_t op, const double* x, double* y, int64_t n, void* st
  *  - A call that returns 0 writes every entry of every non-NULL output array:
  *    all of p_action / svf / value, `status` and `iterations` of every
  *    instance, the outputs of instances whose status is not IRLMX_OK included
- *    (an optional output that is given -- value, log_z0, svf_t -- likewise).
+ *    (an optional output that is given -- value, log_z0, svf_t, value0 -- likewise).
  *    No output entry is read before it is written: outputs may be
  *    uninitialised memory.
  */
@@ -417,6 +418,65 @@ int irlmx_forward_svf_horizon(const irlmx_mdp* mdp, const double* p_initial, con
                               size_t workspace_bytes, void* stream);
 
 /*
+ * Finite-horizon MaxCausalEnt (no reference counterpart beyond the statements
+ * of maxent.py:279-341): the soft Bellman recursion for a fixed number of steps
+ * T = `horizon` -- the causal model of irlmx_soft_backward for worlds without a
+ * terminal state and demonstrations cut after T steps.  It needs no terminal
+ * set and no discount below 1, and there is no convergence test: the sweep
+ * count is T.  Its pi_t has the [B][T][S][A] layout irlmx_forward_svf_horizon
+ * consumes; with p0 . V_0 as the objective, d(p0 . V_0) / d r(s) is that pass's
+ * svf under pi_t, so e_features - svf is the exact likelihood gradient.
+ *
+ * From V_T(s) = r(s), for t = T-1 ... 0, per state s:
+ *   1. Per action a in index order, accumulate
+ *      acc = fma(P[s, target_k(s), a], V_{t+1}(target_k(s)), acc) from 0 over
+ *      every stored slot in slot order.  Then q_a = r(s) + discount * acc, with
+ *      the product rounded before the sum (as irlmx_soft_backward).
+ *   2. v = q_0, then v = softmax2(v, q_a) for a = 1 ... A-1: max + log(1 +
+ *      exp(min - max)) with numpy's exp / log (maxent.py:260-276, 331-333).
+ *      There is no phi start: starting from q_0 equals the reference's
+ *      softmax(-inf, q_0) exactly, without its -inf - -inf.
+ *   3. pi_t(s, a) = np_exp(q_a - v) (maxent.py:341).  With A = 1 every row is 1.0.
+ *   4. V_t(s) = v.  For a terminal s, V_t(s) = r(s) is held, so the state is
+ *      absorbing; pi_t at a terminal s is still the row of step 3 (as the
+ *      non-causal pass's terminal row divides by the sum just formed).
+ * Conventions are those of irlmx_backward_maxent_horizon: a visited state
+ * contributes its reward, the final one included, and with discount = 1 on a
+ * deterministic table the two models coincide (V_0 = log Z_0).
+ *   reward [B][S]; terminal [B][S] or NULL (no terminal state)
+ *   discount   in [0, 1]; NaN or a value outside: IRLMX_EINVAL
+ *   horizon    1 .. 2^20, IRLMX_EINVAL outside
+ *   p_action_t [B][T][S][A] out: pi_t, B * T * S * A * 8 bytes
+ *   value0     [B][S] out or NULL: V_0
+ * Non-finite values spread by IEEE rules in the order above; a zero-weight ELL
+ * padding slot that points at a non-finite V is included (0 * inf = NaN).
+ * status: IRLMX_NONFINITE if and only if the instance's V_0 holds a non-finite
+ * entry, whether or not value0 is given; a non-finite r(s) always reaches
+ * V_0(s).  With finite rewards everything stays finite: the pass works in the
+ * log domain, so there is no extended-range form.
+ *
+ * STENCIL5 and ELL layouts, IRLMX_EINVAL for DENSE.  Two shapes, the same bits
+ * in both, routed as the horizon backward is: one workgroup per instance for
+ * all T steps (V ping-pongs in LDS, one barrier per step) where the model's
+ * (states per thread, slot class) pair is instantiated -- up to 1024 states,
+ * and up to 4096 once the batch holds a workgroup for every CU
+ * (IRLMX_HORIZON_FUSED_BATCH moves that count) -- else one launch per step
+ * with V double-buffered in the workspace (T + 1 launches, no host poll).
+ * Fully asynchronous on `stream`.  Workspace: irlmx_workspace_bytes(mdp,
+ * IRLMX_OP_SOFT_BACKWARD_HORIZON), independent of T.  `workspace_mem`,
+ * `workspace_bytes` are the `workspace`, `workspace_bytes` of the call
+ * contract beside irlmx_workspace_bytes, all of which holds for this entry
+ * (tests/test_gpu_soft_horizon_contract.py holds it to that, through
+ * tests/soft_horizon_call.py: tests/abi_call.py's table and the count that
+ * tests/test_call_contract_host.py reads off the parameter name `workspace`
+ * are those of the eight earlier entry points).
+ */
+int irlmx_soft_backward_horizon(const irlmx_mdp* mdp, const double* reward, const uint8_t* terminal /* may be NULL */,
+                                double discount, int32_t horizon, double* p_action_t /* [B][T][S][A] */,
+                                double* value0 /* [B][S], may be NULL */, int32_t* status, void* workspace_mem,
+                                size_t workspace_bytes, void* stream);
+
+/*
  * Demonstrations on the device (no reference counterpart beyond the statistics
  * of maxent.py:15-60: the reference samples with numpy's global generator,
  * trajectory.py:52-128, which the trajectory.py drop-in follows draw for draw).
@@ -532,7 +592,8 @@ int irlmx_value_iteration_numpy_order(const irlmx_mdp* mdp, const double* reward
  * count); IRLMX_EINVAL for DENSE, here and 0 from irlmx_workspace_bytes.
  * IRLMX_OP_BACKWARD_HORIZON / IRLMX_OP_FORWARD_HORIZON likewise: fused ([5],
  * [7], [8] = 1, [9]) or per sweep ([5] = 1, [7]; [8] = 0: its launch count is
- * the horizon); IRLMX_EINVAL for DENSE.
+ * the horizon); IRLMX_EINVAL for DENSE.  IRLMX_OP_SOFT_BACKWARD_HORIZON uses
+ * the same fields the same way (per sweep its launch count is the horizon + 1).
  * A backward plan assumes rescale != 0 unless op carries IRLMX_PLAN_NO_RESCALE.
  */
 #define IRLMX_PLAN_LEN 10

@@ -5,7 +5,7 @@
 // (with_pair) and launcher (launch_fused), the slot classes, the per-sweep
 // launch grid and the plan rows (fixed_point.hip defines what is not a
 // template; grid.hip, extended_grid.hip, numpy_order.hip, extended.hip,
-// policy_eval.hip and horizon.hip are the other users).
+// policy_eval.hip, horizon.hip and soft_horizon.hip are the other users).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -342,6 +342,9 @@ constexpr bool fused_pair_ok(int op, int spt, int kmax) {
     case IRLMX_OP_VALUE_ITERATION:
       return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 4) || (kmax == 16 && spt == 1) ||
              (kmax == 32 && spt == 1);
+    case IRLMX_OP_SOFT_BACKWARD_HORIZON:  // (soft_horizon.hip: rolled action loop, table re-read every step)
+      return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt <= 2) ||
+             (kmax == 32 && spt == 1);
   }
   return false;
 }
@@ -407,5 +410,14 @@ inline bool horizon_op(int op) { return op == IRLMX_OP_BACKWARD_HORIZON || op ==
 int horizon_check_model(const Model& m, const char* fn);
 size_t horizon_workspace_bytes(const Model& m, int op);
 void horizon_plan(const Model& m, int op, int64_t* plan);
+// Several states per thread run fused only from this many instances on (one
+// workgroup per CU; IRLMX_HORIZON_FUSED_BATCH).
+int horizon_fused_min_batch();
+
+// The finite-horizon soft value iteration (soft_horizon.hip;
+// IRLMX_OP_SOFT_BACKWARD_HORIZON): its workspace and plan; the model check is
+// horizon_check_model.
+size_t soft_horizon_workspace_bytes(const Model& m);
+void soft_horizon_plan(const Model& m, int64_t* plan);
 
 }  // namespace irlmx

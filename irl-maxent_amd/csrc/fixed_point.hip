@@ -1015,6 +1015,8 @@ extern "C" size_t irlmx_workspace_bytes(const irlmx_mdp* mdp, int32_t op) {
   if (extended_op(op)) return check_extended_op(m, op, "workspace_bytes") ? 0 : extended_workspace_bytes(m);
   if (op == IRLMX_OP_POLICY_EVALUATION && policy_eval_check_model(m, "workspace_bytes")) return 0;
   if (horizon_op(op)) return horizon_check_model(m, "workspace_bytes") ? 0 : horizon_workspace_bytes(m, op);
+  if (op == IRLMX_OP_SOFT_BACKWARD_HORIZON)
+    return horizon_check_model(m, "workspace_bytes") ? 0 : soft_horizon_workspace_bytes(m);
   return carve(m, op, nullptr).total;
 }
 
@@ -1031,9 +1033,10 @@ extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* p
   // (a backward call with rescale = 0 never takes the cluster shape: see irlmx_backward_maxent)
   const bool no_rescale = op > 0 && (op & IRLMX_PLAN_NO_RESCALE) != 0;
   if (no_rescale) op &= ~IRLMX_PLAN_NO_RESCALE;
-  // (IRLMX_OP_POLICY_EVALUATION is 6 and the horizon ops 8 and 9: the values between stay the unknown
-  // ops they have always been)
-  if (op < IRLMX_OP_BACKWARD || (op > IRLMX_OP_VALUE_ITERATION && op != IRLMX_OP_POLICY_EVALUATION && !horizon_op(op))) {
+  // (IRLMX_OP_POLICY_EVALUATION is 6, the horizon ops 8 and 9 and the soft horizon op 11: the values
+  // between stay the unknown ops they have always been)
+  if (op < IRLMX_OP_BACKWARD || (op > IRLMX_OP_VALUE_ITERATION && op != IRLMX_OP_POLICY_EVALUATION && !horizon_op(op) &&
+                                 op != IRLMX_OP_SOFT_BACKWARD_HORIZON)) {
     set_error("unknown op %d", op);
     return IRLMX_EINVAL;
   }
@@ -1045,6 +1048,11 @@ extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* p
   if (horizon_op(op)) {
     if (int rc = horizon_check_model(m, "execution_plan")) return rc;
     horizon_plan(m, op, plan);
+    return 0;
+  }
+  if (op == IRLMX_OP_SOFT_BACKWARD_HORIZON) {
+    if (int rc = horizon_check_model(m, "execution_plan")) return rc;
+    soft_horizon_plan(m, plan);
     return 0;
   }
   // (the compact layout is data-dependent: from the table's properties, else checked on the device)

@@ -481,7 +481,7 @@ static size_t hz_fused_lds(const Model& m, int op) {
 // per CU the per-sweep shape is the faster one (measured, DESIGN.md section 4
 // "Finite horizon": 64 x 64 fused / per sweep 2.2 at one instance, 1.5 at 64,
 // 0.8 at 256; at one state per thread fused wins at every batch, 0.1 - 0.9).
-static int hz_fused_min_batch() {
+int horizon_fused_min_batch() {
   const int forced_cus = env_int("IRLMX_PLAN_CUS", 0);
   const int cus = forced_cus > 0 ? forced_cus : device_cus();
   return env_int("IRLMX_HORIZON_FUSED_BATCH", cus > 0 ? cus : 256);
@@ -490,7 +490,7 @@ static int hz_fused_min_batch() {
 static bool hz_fused_shape(const Model& m, int op, FusedShape* out) {
   const bool bwd = op == IRLMX_OP_BACKWARD_HORIZON;
   if (!fused_shape(m, bwd ? IRLMX_OP_BACKWARD : IRLMX_OP_FORWARD, out, false)) return false;
-  if (out->spt > 1 && m.B < hz_fused_min_batch()) return false;
+  if (out->spt > 1 && m.B < horizon_fused_min_batch()) return false;
   return hz_fused_lds(m, op) <= kExtLdsMax;
 }
 

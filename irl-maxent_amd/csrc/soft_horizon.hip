@@ -1,0 +1,270 @@
+// Finite-horizon MaxCausalEnt (irlmx_soft_backward_horizon) on gfx950: the soft
+// Bellman recursion for a fixed number of steps T, with no terminal state, no
+// discount below 1 and no convergence test needed.
+//
+// From V_T(s) = r(s), for t = T-1 .. 0, per state s (include/irlmx.h states the
+// same order word for word):
+//
+//   1. per action a in index order, acc = fma(P[s, target_k(s), a], V_{t+1}(target_k(s)), acc)
+//      from 0 over every stored slot in slot order; q_a = r(s) + discount * acc,
+//      the product rounded before the sum
+//   2. v = q_0, then v = softmax2(v, q_a) for a = 1 .. A-1 (common.h: numpy's exp / log)
+//   3. pi_t(s, a) = np_exp(q_a - v)
+//   4. V_t(s) = v; a terminal s holds V_t(s) = r(s) (absorbing) and keeps the row of step 3
+//
+// q_a rests in the output row between steps 1 and 3 (the action loop stays
+// rolled: 2 (A - 1) + A inlined exp / log per state leave no registers for A
+// values, and a dynamic index into registers would go to scratch), and the table
+// is re-read every step.  Two shapes, the same statements and so the same bits:
+// fused -- one workgroup per instance for all T steps, V ping-pongs in LDS, one
+// barrier per step -- and per sweep: one launch per step over all instances, V
+// double-buffered in the caller's workspace; the launch count is T + 1, so the
+// host never polls.  The pass works in the log domain: finite rewards keep
+// everything finite, and there is no extended-range form.
+
+#include <hip/hip_runtime.h>
+
+#include "fixed_point.h"
+
+namespace irlmx {
+
+constexpr int kShMaxHorizon = 1 << 20;
+
+struct SoftHzArgs {
+  Model m;
+  const double* reward;
+  const uint8_t* term;  // may be null
+  double discount;
+  int T;
+  double* pi;      // [B][T][S][A]
+  double* value0;  // [B][S], may be null
+  int32_t* status;
+};
+
+// per-sweep buffers (the fused kernel keeps V in LDS)
+struct ShWs {
+  double* v[2];  // [B][S] ping and pong
+  size_t total;
+};
+
+__device__ inline size_t sh_pi_row(const Model& m, int T, int b, int t, int s) {
+  return (((size_t)b * T + t) * m.S + s) * m.A;
+}
+
+// One state of one step: writes the policy row `out`, returns v (step 2).
+// KMAX > 0: the slot class is compiled in, and up to 8 slots the slot loop is
+// unrolled (nbr(k) may then be a register copy); from 16 slots on, and with
+// KMAX = 0 (per-sweep shape: any K), the slot loop is rolled.
+template <int KMAX, class Nbr>
+__device__ __attribute__((always_inline)) inline double sh_row(const Model& m, int b, int s, double r, double discount,
+                                                               const double* vin, Nbr&& nbr, const NpTables* tabs,
+                                                               double* out) {
+  const int K = m.K, A = m.A;
+  double v = 0.0;
+#pragma unroll 1
+  for (int act = 0; act < A; ++act) {
+    double acc = 0.0;
+    if constexpr (KMAX > 0 && KMAX <= 8) {
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K) acc = fma(row_val(m, b, act, k, s), vin[nbr(k)], acc);
+    } else {
+#pragma unroll 1
+      for (int k = 0; k < K; ++k) acc = fma(row_val(m, b, act, k, s), vin[nbr(k)], acc);
+    }
+    const double q = __dadd_rn(r, __dmul_rn(discount, acc));
+    out[act] = q;
+    v = act == 0 ? q : softmax2(v, q, tabs);
+  }
+#pragma unroll 1
+  for (int act = 0; act < A; ++act) out[act] = np_exp(__dsub_rn(out[act], v), tabs);  // maxent.py:341
+  return v;
+}
+
+// ---------------------------------------------------------------------------
+// fused shape: one workgroup per instance for all T steps
+// ---------------------------------------------------------------------------
+
+template <int SPT, int KMAX>
+__global__ void __launch_bounds__(1024) soft_hz_fused_kernel(SoftHzArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char soft_hz_smem[];
+  const Model& m = a.m;
+  const int S = m.S, K = m.K, T = a.T;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  NpTables* tabs = (NpTables*)soft_hz_smem;
+  double* vA = (double*)(soft_hz_smem + sizeof(NpTables));
+  double* vB = vA + S;
+
+  // Up to 10 neighbour indices per thread stay in registers with the reward and
+  // the terminal flag (the loop over this thread's states is then unrolled);
+  // beyond that the state loop is rolled and everything per state is read at
+  // its use: held, <4, 5> spills 16 VGPRs and <2, 8> 40 at 1024 threads.
+  constexpr bool kHold = SPT * KMAX <= 10;
+  double r[kHold ? SPT : 1];
+  bool term[kHold ? SPT : 1];
+  int nb[kHold ? SPT : 1][kHold ? KMAX : 1];
+  np_stage_tables(tabs);
+  if constexpr (kHold) {
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      const int s = tid + j * nt;
+      r[j] = 0.0;
+      term[j] = false;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) nb[j][k] = 0;
+      if (s < S) {
+        r[j] = a.reward[(size_t)b * S + s];
+        term[j] = a.term && a.term[(size_t)b * S + s] != 0;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+          if (k < K) nb[j][k] = row_nbr(m, b, s, k);
+      }
+    }
+  }
+  for (int s = tid; s < S; s += nt) vA[s] = a.reward[(size_t)b * S + s];  // V_T = r
+  __syncthreads();
+
+  int nonfinite = 0;
+  for (int it = 0; it < T; ++it) {
+    const int t = T - 1 - it;
+    const double* vin = (it & 1) ? vB : vA;
+    double* vout = (it & 1) ? vA : vB;
+    auto state = [&](int s, double rs, bool ts, auto&& nbr) __attribute__((always_inline)) {
+      double v = sh_row<KMAX>(m, b, s, rs, a.discount, vin, nbr, tabs, a.pi + sh_pi_row(m, T, b, t, s));
+      if (ts) v = rs;  // absorbing: V_t = r, held
+      vout[s] = v;
+      if (t == 0) {
+        if (a.value0) a.value0[(size_t)b * S + s] = v;
+        nonfinite |= !isfinite(v);
+      }
+    };
+    if constexpr (kHold) {
+#pragma unroll
+      for (int j = 0; j < SPT; ++j) {
+        const int s = tid + j * nt;
+        if (s < S) state(s, r[j], term[j], [&](int k) __attribute__((always_inline)) { return nb[j][k]; });
+      }
+    } else {
+#pragma unroll 1
+      for (int s = tid; s < S; s += nt)
+        state(s, a.reward[(size_t)b * S + s], a.term && a.term[(size_t)b * S + s] != 0,
+              [&](int k) __attribute__((always_inline)) { return row_nbr(m, b, s, k); });
+    }
+    __syncthreads();
+  }
+  nonfinite = __syncthreads_or(nonfinite);
+  if (tid == 0) a.status[b] = nonfinite ? IRLMX_NONFINITE : IRLMX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// per-sweep shape: one launch per step over all instances
+// ---------------------------------------------------------------------------
+
+__global__ void soft_hz_init_kernel(SoftHzArgs a, ShWs ws) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  if (s >= a.m.S) return;
+  const size_t i = (size_t)b * a.m.S + s;
+  ws.v[0][i] = a.reward[i];
+  if (s == 0) a.status[b] = IRLMX_OK;
+}
+
+__global__ void __launch_bounds__(kSweepThreads) soft_hz_step_kernel(SoftHzArgs a, ShWs ws, int t, int odd) {
+  const Model& m = a.m;
+  const int S = m.S;
+  const int b = blockIdx.y;
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const size_t i = (size_t)b * S + s;
+  const double r = a.reward[i];
+  double v = sh_row<0>(m, b, s, r, a.discount, ws.v[odd] + (size_t)b * S,
+                       [&](int k) __attribute__((always_inline)) { return row_nbr(m, b, s, k); }, &kNpTabs,
+                       a.pi + sh_pi_row(m, a.T, b, t, s));
+  if (a.term && a.term[i]) v = r;
+  ws.v[odd ^ 1][i] = v;
+  if (t == 0) {
+    if (a.value0) a.value0[i] = v;
+    if (!isfinite(v)) atomicOr(&a.status[b], IRLMX_NONFINITE);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host-side dispatch
+// ---------------------------------------------------------------------------
+
+// fused_pair_ok(IRLMX_OP_SOFT_BACKWARD_HORIZON, ..) is the instantiation list
+// (fixed_point.h; the register table is in DESIGN.md section 4).
+static void (*soft_hz_fn(int spt, int kmax))(SoftHzArgs) {
+  return with_pair<void (*)(SoftHzArgs)>(spt, kmax, [](auto s, auto k) {
+    if constexpr (fused_pair_ok(IRLMX_OP_SOFT_BACKWARD_HORIZON, s, k)) return &soft_hz_fused_kernel<s, k>;
+    else return nullptr;
+  });
+}
+
+// the NpTables copy, then V ping and pong: 16 B per state
+static size_t soft_hz_fused_lds(const Model& m) { return sizeof(NpTables) + 2 * (size_t)m.S * sizeof(double); }
+
+// The fused shape of the pass: the non-causal horizon backward's rule
+// (horizon_fused_min_batch: several states per thread only from one workgroup
+// per CU on), over this pass's own pair list.
+static bool soft_hz_fused_shape(const Model& m, FusedShape* out) {
+  if (!fused_shape(m, IRLMX_OP_SOFT_BACKWARD_HORIZON, out, false)) return false;
+  return out->spt == 1 || m.B >= horizon_fused_min_batch();
+}
+
+static ShWs soft_hz_carve(const Model& m, void* base) {
+  ShWs w;
+  Carver c{(char*)base};
+  FusedShape fs;
+  const bool sweep = !soft_hz_fused_shape(m, &fs);
+  for (int i = 0; i < 2; ++i) w.v[i] = c.take<double>(sweep ? (size_t)m.B * m.S * sizeof(double) : 0);
+  w.total = c.total();
+  return w;
+}
+
+size_t soft_horizon_workspace_bytes(const Model& m) { return soft_hz_carve(m, nullptr).total; }
+
+void soft_horizon_plan(const Model& m, int64_t* plan) {
+  FusedShape fs;
+  if (soft_hz_fused_shape(m, &fs)) return plan_fused(plan, fs, soft_hz_fused_lds(m));
+  plan_sweep(plan, 1, 0);  // one state per lane; the launch count is the horizon + 1
+}
+
+}  // namespace irlmx
+
+using namespace irlmx;
+
+extern "C" int irlmx_soft_backward_horizon(const irlmx_mdp* mdp, const double* reward, const uint8_t* terminal,
+                                           double discount, int32_t horizon, double* p_action_t, double* value0,
+                                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "soft_backward_horizon";
+  if (int rc = validate(mdp)) return rc;
+  const Model m = make_model(mdp);
+  if (int rc = horizon_check_model(m, fn)) return rc;
+  if (int rc = need_all(fn, {{reward, "reward"}, {p_action_t, "p_action_t"}, {status, "status"}})) return rc;
+  if (!(discount >= 0.0 && discount <= 1.0)) {  // NaN too
+    set_error("%s: discount %g outside [0, 1]", fn, discount);
+    return IRLMX_EINVAL;
+  }
+  if (horizon < 1 || horizon > kShMaxHorizon) {
+    set_error("%s: horizon %d outside [1, %d]", fn, horizon, kShMaxHorizon);
+    return IRLMX_EINVAL;
+  }
+  if (int rc = check_ws(soft_hz_carve(m, nullptr).total, workspace_bytes, workspace)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  SoftHzArgs a{m, reward, terminal, discount, horizon, p_action_t, value0, status};
+  FusedShape fs;
+  if (soft_hz_fused_shape(m, &fs)) {
+    void (*kfn)(SoftHzArgs) = soft_hz_fn(fs.spt, fs.kmax);
+    if (!kfn) { set_error("no soft horizon fused kernel for spt=%d kmax=%d", fs.spt, fs.kmax); return IRLMX_EINVAL; }
+    return launch_fused(kfn, "soft_hz_fused_kernel", m.B, fs.threads, soft_hz_fused_lds(m), st, a);
+  }
+  const ShWs ws = soft_hz_carve(m, workspace);
+  count_event(IRLMX_CTR_SWEEP_CALLS);
+  const dim3 g = sweep_grid(m);
+  hipLaunchKernelGGL(soft_hz_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
+  for (int it = 0; it < horizon; ++it)
+    hipLaunchKernelGGL(soft_hz_step_kernel, g, dim3(kSweepThreads), 0, st, a, ws, horizon - 1 - it, it & 1);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : hip_fail(e, "soft horizon backward");
+}

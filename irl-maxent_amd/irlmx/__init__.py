@@ -18,6 +18,6 @@ from . import ops  # noqa: F401
 from .ops import backward_maxent_extended, execution_plan  # noqa: F401
 from .ops import expected_value_difference, policy_evaluation  # noqa: F401
 from .ops import demo_log_likelihood, rollout  # noqa: F401
-from .ops import backward_maxent_horizon, forward_svf_horizon  # noqa: F401
+from .ops import backward_maxent_horizon, forward_svf_horizon, soft_backward_horizon  # noqa: F401
 
 __version__ = "0.1.0"

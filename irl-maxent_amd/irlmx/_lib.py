@@ -26,6 +26,7 @@ OK, NONFINITE, MAXITER = 0, 1, 2
 OP_BACKWARD, OP_FORWARD, OP_SOFT_BACKWARD, OP_VALUE_ITERATION = 1, 2, 3, 4
 OP_POLICY_EVALUATION = 6   # (5 is not an op: the library has always answered "unknown op 5")
 OP_BACKWARD_HORIZON, OP_FORWARD_HORIZON = 8, 9   # (7 is not an op either)
+OP_SOFT_BACKWARD_HORIZON = 11   # (10 is not an op either)
 HORIZON_MAX = 1 << 20
 PLAN_NO_RESCALE = 0x100
 PLAN_EXTENDED_RANGE = 0x200
@@ -92,7 +93,8 @@ SIGNATURES = {
     "irlmx_policy_evaluation": (ctypes.c_int, [_MDP, _P, _P, _P, _D, _D, _I64, _P, _P, _P, _P, _SZ, _P]),
     "irlmx_backward_maxent_horizon": (ctypes.c_int, [_MDP, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "irlmx_forward_svf_horizon": (ctypes.c_int, [_MDP, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
-    "irlmx_rollout": (ctypes.c_int, [_MDP, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "irlmx_soft_backward_horizon": (ctypes.c_int, [_MDP, _P, _P, _D, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "irlmx_rollout":(ctypes.c_int, [_MDP, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "irlmx_demo_statistics": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "irlmx_demo_log_likelihood": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "irlmx_execution_plan": (ctypes.c_int, [_MDP, _I32, _P]),

@@ -60,7 +60,9 @@ trajectories).  ``backward()`` returns the time-indexed policy [n, T, S, A]
 instance at T = 128) and ``forward()`` sums the T + 1 marginals
 (``ops.forward_svf_horizon``), both fully asynchronous; ``terminal`` may be
 empty; ``extended_range`` is ignored, the pass always keeps one exponent per
-state.
+state.  ``BatchedCausalHorizon`` is the same driver with the finite-horizon
+soft value iteration as its backward pass (``ops.soft_backward_horizon``): the
+MaxCausalEnt model, for stochastic dynamics.
 """
 
 import numpy as np
@@ -104,8 +106,8 @@ class BatchedMaxEnt:
         ``causal=True``."""
         if horizon is not None:
             if causal:
-                raise ValueError("horizon applies to the non-causal model only (a finite-horizon soft value "
-                                 "iteration is not implemented)")
+                raise ValueError("horizon applies to the non-causal model only (the finite-horizon causal model "
+                                 "is BatchedCausalHorizon)")
             if int(horizon) != horizon or not 1 <= int(horizon) <= (1 << 20):
                 raise ValueError(f"horizon must be an integer in [1, 2^20], got {horizon!r}")
             horizon = int(horizon)
@@ -394,3 +396,32 @@ class BatchedMaxEnt:
             if on_step is not None:
                 on_step(self)
         return self.reward(), self.steps
+
+
+class BatchedCausalHorizon(BatchedMaxEnt):
+    """Finite-horizon MaxCausalEnt IRL: ``BatchedMaxEnt(horizon=T)`` with the soft
+    Bellman recursion over T steps as its backward pass
+    (``ops.soft_backward_horizon``) -- the model for stochastic dynamics and
+    demonstrations of a fixed length.  ``terminal`` may be empty and
+    ``discount`` may be 1: the recursion needs neither to be well posed.  The
+    forward pass, the update, compaction and ``from_trajectories`` (``horizon``
+    and ``discount`` go through its ``**kw``) are the base class's;
+    ``e_features - svf`` is the exact gradient of the demonstrations'
+    likelihood.  ``log_likelihood`` and ``expected_value_difference`` raise
+    NotImplementedError, as with any time-indexed policy."""
+
+    def __init__(self, mdp, e_features, p_initial, terminal, horizon, discount=1.0, **kw):
+        if kw.pop("causal", False):
+            raise ValueError("BatchedCausalHorizon is the causal model already: causal= is not an argument")
+        discount = float(discount)
+        if not 0.0 <= discount <= 1.0:
+            raise ValueError(f"discount must lie in [0, 1], got {discount!r}")
+        super().__init__(mdp, e_features, p_initial, terminal, horizon=horizon, **kw)
+        if self.horizon is None:
+            raise ValueError("BatchedCausalHorizon needs a horizon")
+        self.discount = discount
+
+    def backward(self):
+        """The time-indexed policy [n, T, S, A] of the working set."""
+        r = self.reward(self._theta_w(), self._w("features"))
+        return ops.soft_backward_horizon(self._w("mdp"), r, self.discount, self.horizon, self._w("terminal"))

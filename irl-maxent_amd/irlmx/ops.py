@@ -32,14 +32,15 @@ PLAN_FIELDS = ("shape", "R", "G", "C", "per_launch", "spt", "layout", "threads",
 SHAPES = {0: "fused", 1: "cluster", 2: "sweep", 3: "dense", 4: "dense-gemm", 5: "grid", 6: "dense-grid"}
 _OPS = {"backward": _lib.OP_BACKWARD, "forward": _lib.OP_FORWARD, "soft_backward": _lib.OP_SOFT_BACKWARD,
         "value_iteration": _lib.OP_VALUE_ITERATION, "policy_evaluation": _lib.OP_POLICY_EVALUATION,
-        "backward_horizon": _lib.OP_BACKWARD_HORIZON, "forward_horizon": _lib.OP_FORWARD_HORIZON}
+        "backward_horizon": _lib.OP_BACKWARD_HORIZON, "forward_horizon": _lib.OP_FORWARD_HORIZON,
+        "soft_backward_horizon": _lib.OP_SOFT_BACKWARD_HORIZON}
 _OPS.update({code: code for code in list(_OPS.values())})   # the _lib.OP_* codes themselves are accepted too
 
 
 def execution_plan(mdp, op, rescale=True, extended_range=False):
     """The kernel plan a call of ``op`` ("backward", "forward", "soft_backward",
     "value_iteration", "policy_evaluation", "backward_horizon",
-    "forward_horizon", or its ``_lib.OP_*`` code) on ``mdp``
+    "forward_horizon", "soft_backward_horizon", or its ``_lib.OP_*`` code) on ``mdp``
     runs on the current device (irlmx_execution_plan):
     shape, tile rows R, ghost rows G, tiles per instance C, instances per launch,
     states per lane, in-tile layout, threads, sequential launches, LDS bytes.
@@ -362,6 +363,35 @@ def backward_maxent_horizon(mdp, reward, horizon, terminal=None, return_log_z0=F
     return (pi, lz) if return_log_z0 else pi
 
 
+def soft_backward_horizon(mdp, reward, discount, horizon, terminal=None, return_value0=False):
+    """Time-indexed policy ``pi_t`` [B, T, S, A] of the finite-horizon
+    MaxCausalEnt model with ``T = horizon`` steps (irlmx_soft_backward_horizon):
+    from ``V_T = r``, for t = T-1 .. 0, ``q_a = r + discount * (P_a V_{t+1})``,
+    ``V_t = softmax_a q_a`` (the reference's pairwise fold, numpy's exp / log)
+    and ``pi_t = exp(q_a - V_t)``.  No terminal state, no discount below 1 and
+    no convergence test are needed (``terminal=None``, ``discount`` in [0, 1]);
+    with a uint8 [B, S] mask (:func:`terminal_mask`) those states are
+    absorbing, ``V_t = r``.  ``return_value0``: returns ``(pi_t, V_0 [B, S])``.
+    :func:`forward_svf_horizon` under ``pi_t`` gives the gradient of ``p0 . V_0``
+    with respect to the reward.
+
+    Memory: the result is ``B * T * S * A * 8`` bytes.  STENCIL5 and ELL models;
+    ``execution_plan(mdp, "soft_backward_horizon")`` names the shape."""
+    lib = _lib.load()
+    B, S, A, T = mdp.batch, mdp.n_states, mdp.n_actions, int(horizon)
+    r = _f64(reward, mdp, (B, S))
+    term = _optional_mask(terminal, mdp)
+    ok = 1 <= T <= _lib.HORIZON_MAX      # (else the call below raises: nothing of size T is allocated)
+    pi = torch.empty((B, T if ok else 1, S, A), dtype=torch.float64, device=mdp.device)
+    v0 = torch.empty((B, S), dtype=torch.float64, device=mdp.device) if return_value0 else None
+    status = torch.empty(B, dtype=torch.int32, device=mdp.device)
+    ws, n = _workspace(mdp, _lib.OP_SOFT_BACKWARD_HORIZON)
+    _lib.check(lib.irlmx_soft_backward_horizon(mdp.struct(), _lib.ptr(r), _lib.ptr(term), float(discount), T,
+                                               _lib.ptr(pi), _lib.ptr(v0), _lib.ptr(status), _lib.ptr(ws), n,
+                                               _lib.stream_ptr(mdp.device)), "soft_backward_horizon")
+    return (pi, v0) if return_value0 else pi
+
+
 def forward_svf_horizon(mdp, p_initial, p_action_t, terminal=None, return_marginals=False):
     """Expected state visitation of T steps under the time-indexed policy
     ``p_action_t`` [B, T, S, A] (irlmx_forward_svf_horizon): ``d_0 = p0``,
@@ -618,5 +648,6 @@ def stochastic_policy(successor, weighted_value):
 
 
 __all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "backward_maxent_extended", "backward_maxent_horizon", "forward_svf", "forward_svf_horizon", "soft_backward",
+           "soft_backward_horizon",
            "value_iteration", "policy_evaluation", "expected_value_difference", "rollout", "rollout_seeds",
            "demo_statistics", "demo_log_likelihood", "RolloutResult", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]

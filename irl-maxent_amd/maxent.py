@@ -40,7 +40,12 @@ Beyond the reference: ``local_action_probabilities_horizon``,
 ``compute_expected_svf_horizon`` and ``irl_horizon`` are the finite-horizon
 form of the same model (``ops.backward_maxent_horizon``,
 ``ops.forward_svf_horizon``), for worlds without a terminal state
-(``terminal=[]``) and demonstrations of a fixed length.
+(``terminal=[]``) and demonstrations of a fixed length;
+``local_causal_action_probabilities_horizon``,
+``compute_expected_causal_svf_horizon`` and ``irl_causal_horizon`` are its
+MaxCausalEnt counterpart for stochastic dynamics (``ops.soft_backward_horizon``:
+the soft Bellman recursion over T steps, no terminal set or discount below 1
+needed).
 """
 
 import os
@@ -55,7 +60,8 @@ __all__ = ["feature_expectation_from_trajectories", "initial_probabilities_from_
            "expected_svf_from_policy", "local_action_probabilities", "compute_expected_svf",
            "expected_svf", "irl", "softmax", "local_causal_action_probabilities",
            "compute_expected_causal_svf", "irl_causal", "local_action_probabilities_horizon",
-           "compute_expected_svf_horizon", "irl_horizon"]
+           "compute_expected_svf_horizon", "irl_horizon", "local_causal_action_probabilities_horizon",
+           "compute_expected_causal_svf_horizon", "irl_causal_horizon"]
 
 
 def _rescale():
@@ -251,6 +257,42 @@ def irl_horizon(p_transition, features, terminal, trajectories, optim, init, hor
 
     def svf_fn(m, reward, term, p0):
         pi = ops.backward_maxent_horizon(m, reward, horizon, term_h)
+        svf, _, _ = ops.forward_svf_horizon(m, p0, pi, term_h)
+        return _host(svf)
+
+    return _irl_loop(mdp, features, terminal, trajectories, optim, init, eps, svf_fn)
+
+
+def local_causal_action_probabilities_horizon(p_transition, terminal, reward, discount, horizon):
+    """Time-indexed policy exp(Q_t - V_t) [T, S, A] of the finite-horizon
+    MaxCausalEnt model with ``T = horizon`` steps (``ops.soft_backward_horizon``):
+    the model for stochastic dynamics; ``terminal`` may be ``[]`` and
+    ``discount`` may be 1."""
+    mdp = _model(p_transition)
+    return _host(ops.soft_backward_horizon(mdp, reward, discount, horizon, _horizon_mask(mdp, terminal)))
+
+
+def compute_expected_causal_svf_horizon(p_transition, p_initial, terminal, reward, discount, horizon):
+    """Expected state visitation over the T + 1 states of a ``horizon``-step
+    trajectory under the finite-horizon MaxCausalEnt policy: the soft Bellman
+    recursion, then ``ops.forward_svf_horizon``."""
+    mdp = _model(p_transition)
+    term = _horizon_mask(mdp, terminal)
+    pi = ops.soft_backward_horizon(mdp, reward, discount, horizon, term)
+    svf, _, _ = ops.forward_svf_horizon(mdp, p_initial, pi, term)
+    return _host(svf)
+
+
+def irl_causal_horizon(p_transition, features, terminal, trajectories, optim, init, discount, horizon, eps=1e-4):
+    """MaxCausalEnt IRL with the finite-horizon model: ``irl_causal``'s gradient
+    ascent, the expected visitation from ``compute_expected_causal_svf_horizon``
+    (the exact gradient of the demonstrations' likelihood).  For demonstrations
+    of ``horizon`` steps each; ``terminal`` may be ``[]``."""
+    mdp = _model(p_transition)
+    term_h = _horizon_mask(mdp, terminal)
+
+    def svf_fn(m, reward, term, p0):
+        pi = ops.soft_backward_horizon(m, reward, discount, horizon, term_h)
         svf, _, _ = ops.forward_svf_horizon(m, p0, pi, term_h)
         return _host(svf)
 

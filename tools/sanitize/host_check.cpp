@@ -34,6 +34,11 @@
 //    and of the backward-only flags, and every validation path of
 //    irlmx_backward_maxent_horizon and irlmx_forward_svf_horizon (NULL arrays,
 //    the optional ones, a horizon outside [1, 2^20], short workspace);
+//  * the finite-horizon soft value iteration (soft_horizon.hip): every
+//    validation path of irlmx_soft_backward_horizon (NULL arrays, the optional
+//    ones, a discount outside [0, 1] or NaN, a horizon outside [1, 2^20], DENSE
+//    tables, short workspace) and the plan and workspace of
+//    IRLMX_OP_SOFT_BACKWARD_HORIZON on a fused and a per-sweep model;
 //  * the demonstration calls (rollout.hip): every validation path of
 //    irlmx_rollout (NULL arrays, n_traj, max_len below 1 and above its cap,
 //    states without actions, DENSE tables), irlmx_demo_statistics and
@@ -45,6 +50,7 @@
 // every model and op of that sweep (dump_plans), to compare two builds of the
 // library -- before and after a change to the planners -- byte for byte.
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -374,6 +380,12 @@ static int run_hzf(const irlmx_mdp* m, void* p0, void* term, void* pi, int horiz
                                    (double*)svf_t, (int32_t*)status, ws, n, nullptr);
 }
 
+static int run_shz(const irlmx_mdp* m, void* reward, void* term, double discount, int horizon, void* pi, void* v0,
+                   void* status, void* ws, size_t n) {
+  return irlmx_soft_backward_horizon(m, (const double*)reward, (const uint8_t*)term, discount, horizon, (double*)pi,
+                                     (double*)v0, (int32_t*)status, ws, n, nullptr);
+}
+
 static int run_roll(const irlmx_mdp* m, int n_traj, int max_len, void* pi, void* term, void* start, void* seed,
                     void* visits, void* starts, void* lengths, void* status, void* states, void* actions) {
   return irlmx_rollout(m, (const double*)pi, (const uint8_t*)term, (const int32_t*)start, (const uint64_t*)seed, n_traj,
@@ -532,6 +544,49 @@ static void error_paths() {
     expect(irlmx_execution_plan(&wide, IRLMX_OP_FORWARD_HORIZON, p), IRLMX_OK, "", "horizon forward plan K_c = 3");
     CHECK(p[0] == IRLMX_SHAPE_FUSED, "horizon forward plan K_c = 3: shape %lld", (long long)p[0]);
     expect(irlmx_execution_plan(&good, IRLMX_OP_FORWARD_HORIZON + 1, p), IRLMX_EINVAL, "unknown op 10", "op 10");
+  }
+  {  // irlmx_soft_backward_horizon: every validation path, in the order the entry checks them
+    const int op = IRLMX_OP_SOFT_BACKWARD_HORIZON;
+    irlmx_mdp big = stencil(128, 40, 4, 2, 0);  // per sweep: V's two buffers (a fused model needs no workspace)
+    const size_t n = irlmx_workspace_bytes(&big, op);
+    CHECK(n >= 2 * 2 * 5120 * sizeof(double) && n % 256 == 0, "soft horizon workspace of a per-sweep model: %zu", n);
+    CHECK(irlmx_workspace_bytes(&good, op) == 0, "soft horizon workspace of a fused model");
+    expect(run_shz(nullptr, f, f, 0.9, 8, f, f, f, f, n), IRLMX_EINVAL, "mdp is NULL", "soft horizon null mdp");
+    for (const Bad& b : bad) {
+      expect(run_shz(&b.m, f, f, 0.9, 8, f, f, f, f, n), IRLMX_EINVAL, b.msg, b.name);
+      CHECK(irlmx_workspace_bytes(&b.m, op) == 0, "%s: soft horizon workspace of an invalid model", b.name);
+    }
+    int64_t p[IRLMX_PLAN_LEN];
+    irlmx_mdp d = dense(25, 4, 1);
+    expect(run_shz(&d, f, f, 0.9, 8, f, f, f, f, n), IRLMX_EINVAL,
+           "soft_backward_horizon: the finite-horizon passes do not run the DENSE", "soft horizon dense");
+    expect(irlmx_execution_plan(&d, op, p), IRLMX_EINVAL, "execution_plan: the finite-horizon passes do not run the DENSE",
+           "soft horizon plan of a DENSE table");
+    CHECK(irlmx_workspace_bytes(&d, op) == 0, "soft horizon workspace of a DENSE table");
+    expect(run_shz(&big, nullptr, f, 0.9, 8, f, f, f, f, n), IRLMX_EINVAL, "soft_backward_horizon: reward is NULL", "soft horizon null reward");
+    expect(run_shz(&big, f, f, 0.9, 8, nullptr, f, f, f, n), IRLMX_EINVAL, "p_action_t is NULL", "soft horizon null p_action_t");
+    expect(run_shz(&big, f, f, 0.9, 8, f, f, nullptr, f, n), IRLMX_EINVAL, "status is NULL", "soft horizon null status");
+    for (double g : {-0.1, 1.5, (double)NAN, (double)INFINITY})
+      expect(run_shz(&big, f, f, g, 8, f, f, f, f, n), IRLMX_EINVAL, "outside [0, 1]", "soft horizon discount out of range");
+    for (int h : {0, -1, (1 << 20) + 1})
+      expect(run_shz(&big, f, f, 0.9, h, f, f, f, f, n), IRLMX_EINVAL, "outside [1, 1048576]", "soft horizon out of range");
+    // terminal and value0 may be NULL, the discount 0 or 1: the calls get as far as the workspace check
+    expect(run_shz(&big, f, nullptr, 1.0, 1 << 20, f, nullptr, f, f, n - 1), IRLMX_EWORKSPACE, "workspace too small",
+           "soft horizon short workspace (terminal and value0 NULL are legal)");
+    expect(run_shz(&big, f, f, 0.0, 8, f, f, f, nullptr, n), IRLMX_EWORKSPACE, "workspace too small", "soft horizon null workspace");
+    expect(irlmx_execution_plan(&good, op, p), IRLMX_OK, "", "soft horizon plan of a fused model");
+    CHECK(p[0] == IRLMX_SHAPE_FUSED && p[5] == 1 && p[8] == 1 && p[9] == 1536 + 16 * (int64_t)good.n_states,
+          "soft horizon fused plan: shape %lld spt %lld LDS %lld", (long long)p[0], (long long)p[5], (long long)p[9]);
+    expect(irlmx_execution_plan(&big, op, p), IRLMX_OK, "", "soft horizon plan of a per-sweep model");
+    CHECK(p[0] == IRLMX_SHAPE_SWEEP && p[5] == 1 && p[7] == 256 && p[8] == 0 && p[9] == 0, "soft horizon sweep plan");
+    irlmx_mdp wide = ell(100, 4, 40, 3, 2);  // more row slots than any fused kernel holds
+    expect(irlmx_execution_plan(&wide, op, p), IRLMX_OK, "", "soft horizon plan K = 40");
+    CHECK(p[0] == IRLMX_SHAPE_SWEEP, "soft horizon plan K = 40: shape %lld", (long long)p[0]);
+    expect(irlmx_execution_plan(&good, op | IRLMX_PLAN_EXTENDED_RANGE, p), IRLMX_EINVAL, "IRLMX_OP_BACKWARD only",
+           "extended flag on the soft horizon op");
+    expect(irlmx_execution_plan(&good, op | IRLMX_PLAN_NO_RESCALE, p), IRLMX_EINVAL, "NO_RESCALE",
+           "no-rescale flag on the soft horizon op");
+    expect(irlmx_execution_plan(&good, 99, p), IRLMX_EINVAL, "unknown op 99", "op 99");
   }
   {  // irlmx_rollout, irlmx_demo_statistics, irlmx_demo_log_likelihood: every validation path
     expect(run_roll(nullptr, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "mdp is NULL", "rollout null mdp");
@@ -694,7 +749,8 @@ static void dump_plans() {
                                      {"IRLMX_EXT_GRID_MAX_LAUNCHES", "1000"}};
   const int ops[] = {IRLMX_OP_BACKWARD, IRLMX_OP_FORWARD, IRLMX_OP_SOFT_BACKWARD, IRLMX_OP_VALUE_ITERATION,
                      IRLMX_OP_BACKWARD | IRLMX_PLAN_NO_RESCALE, IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE,
-                     IRLMX_OP_POLICY_EVALUATION, IRLMX_OP_BACKWARD_HORIZON, IRLMX_OP_FORWARD_HORIZON};
+                     IRLMX_OP_POLICY_EVALUATION, IRLMX_OP_BACKWARD_HORIZON, IRLMX_OP_FORWARD_HORIZON,
+                     IRLMX_OP_SOFT_BACKWARD_HORIZON};
   for (const auto& sw : switches) {
     if (sw[0]) setenv(sw[0], sw[1], 1);
     for_each_model([&](const irlmx_mdp& m, const char* tag) {
