@@ -463,17 +463,11 @@ int irlmx_forward_svf_horizon(const irlmx_mdp* mdp, const double* p_initial, con
  * (IRLMX_HORIZON_FUSED_BATCH moves that count) -- else one launch per step
  * with V double-buffered in the workspace (T + 1 launches, no host poll).
  * Fully asynchronous on `stream`.  Workspace: irlmx_workspace_bytes(mdp,
- * IRLMX_OP_SOFT_BACKWARD_HORIZON), independent of T.  `workspace_mem`,
- * `workspace_bytes` are the `workspace`, `workspace_bytes` of the call
- * contract beside irlmx_workspace_bytes, all of which holds for this entry
- * (tests/test_gpu_soft_horizon_contract.py holds it to that, through
- * tests/soft_horizon_call.py: tests/abi_call.py's table and the count that
- * tests/test_call_contract_host.py reads off the parameter name `workspace`
- * are those of the eight earlier entry points).
+ * IRLMX_OP_SOFT_BACKWARD_HORIZON), independent of T.
  */
 int irlmx_soft_backward_horizon(const irlmx_mdp* mdp, const double* reward, const uint8_t* terminal /* may be NULL */,
                                 double discount, int32_t horizon, double* p_action_t /* [B][T][S][A] */,
-                                double* value0 /* [B][S], may be NULL */, int32_t* status, void* workspace_mem,
+                                double* value0 /* [B][S], may be NULL */, int32_t* status, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
 /*

@@ -403,21 +403,17 @@ void extended_plan(const Model& m, int64_t* plan);
 // IRLMX_EINVAL and the message, prefixed by `fn`).
 int policy_eval_check_model(const Model& m, const char* fn);
 
-// The finite-horizon passes (horizon.hip; op IRLMX_OP_BACKWARD_HORIZON or
-// IRLMX_OP_FORWARD_HORIZON): whether this model is one they run (else
+// The three finite-horizon passes (horizon.hip, soft_horizon.hip; the rest of
+// their host side is horizon.h): whether this model is one they run (else
 // IRLMX_EINVAL and the message, prefixed by `fn`), their workspace and plan.
-inline bool horizon_op(int op) { return op == IRLMX_OP_BACKWARD_HORIZON || op == IRLMX_OP_FORWARD_HORIZON; }
+inline bool horizon_op(int op) {
+  return op == IRLMX_OP_BACKWARD_HORIZON || op == IRLMX_OP_FORWARD_HORIZON || op == IRLMX_OP_SOFT_BACKWARD_HORIZON;
+}
 int horizon_check_model(const Model& m, const char* fn);
 size_t horizon_workspace_bytes(const Model& m, int op);
 void horizon_plan(const Model& m, int op, int64_t* plan);
 // Several states per thread run fused only from this many instances on (one
 // workgroup per CU; IRLMX_HORIZON_FUSED_BATCH).
 int horizon_fused_min_batch();
-
-// The finite-horizon soft value iteration (soft_horizon.hip;
-// IRLMX_OP_SOFT_BACKWARD_HORIZON): its workspace and plan; the model check is
-// horizon_check_model.
-size_t soft_horizon_workspace_bytes(const Model& m);
-void soft_horizon_plan(const Model& m, int64_t* plan);
 
 }  // namespace irlmx

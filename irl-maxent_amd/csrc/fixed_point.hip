@@ -1000,59 +1000,69 @@ static bool bwd_compact(const Model& m, int* flag, hipStream_t st) {
 // bit is set: those stay "unknown op")
 static bool extended_op(int op) { return op > 0 && (op & IRLMX_PLAN_EXTENDED_RANGE) != 0; }
 
-// The flag goes with IRLMX_OP_BACKWARD alone, on a model the extended pass runs.
-static int check_extended_op(const Model& m, int op, const char* fn) {
-  if (op != (IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE)) {
-    set_error("IRLMX_PLAN_EXTENDED_RANGE applies to IRLMX_OP_BACKWARD only (and not with IRLMX_PLAN_NO_RESCALE)");
-    return IRLMX_EINVAL;
+// What the two model queries ask about an op (IRLMX_OP_*, with
+// IRLMX_PLAN_EXTENDED_RANGE where it applies): a new op is one more case here.
+struct OpQueries {
+  bool known = false;                                             // (5, 7 and 10 stay the unknown ops they have always been)
+  int (*check_model)(const Model& m, const char* fn) = nullptr;   // null: every model
+  size_t (*bytes)(const Model& m, int op) = nullptr;              // null: carve(m, op).total
+  void (*plan)(const Model& m, int op, int64_t* plan) = nullptr;  // null: the row of route(m, op)
+};
+static OpQueries op_queries(int op) {
+  switch (op) {
+    case IRLMX_OP_BACKWARD:
+    case IRLMX_OP_FORWARD:
+    case IRLMX_OP_SOFT_BACKWARD:
+    case IRLMX_OP_VALUE_ITERATION:
+      return {true};
+    case IRLMX_OP_POLICY_EVALUATION:
+      return {true, policy_eval_check_model};
+    case IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE:
+      return {true, extended_check_model, [](const Model& m, int) { return extended_workspace_bytes(m); },
+              [](const Model& m, int, int64_t* plan) { extended_plan(m, plan); }};
+    case IRLMX_OP_BACKWARD_HORIZON:
+    case IRLMX_OP_FORWARD_HORIZON:
+    case IRLMX_OP_SOFT_BACKWARD_HORIZON:
+      return {true, horizon_check_model, horizon_workspace_bytes, horizon_plan};
   }
-  return extended_check_model(m, fn);
+  return {};
 }
 
+// The extended-range flag goes with IRLMX_OP_BACKWARD alone.
+static int check_extended_flag(int op) {
+  if (!extended_op(op) || op == (IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE)) return 0;
+  set_error("IRLMX_PLAN_EXTENDED_RANGE applies to IRLMX_OP_BACKWARD only (and not with IRLMX_PLAN_NO_RESCALE)");
+  return IRLMX_EINVAL;
+}
+
+// (an op this does not know is sized as carve() sizes it)
 extern "C" size_t irlmx_workspace_bytes(const irlmx_mdp* mdp, int32_t op) {
   if (validate(mdp)) return 0;
   const Model m = make_model(mdp);
-  if (extended_op(op)) return check_extended_op(m, op, "workspace_bytes") ? 0 : extended_workspace_bytes(m);
-  if (op == IRLMX_OP_POLICY_EVALUATION && policy_eval_check_model(m, "workspace_bytes")) return 0;
-  if (horizon_op(op)) return horizon_check_model(m, "workspace_bytes") ? 0 : horizon_workspace_bytes(m, op);
-  if (op == IRLMX_OP_SOFT_BACKWARD_HORIZON)
-    return horizon_check_model(m, "workspace_bytes") ? 0 : soft_horizon_workspace_bytes(m);
-  return carve(m, op, nullptr).total;
+  if (check_extended_flag(op)) return 0;
+  const OpQueries q = op_queries(op);
+  if (q.check_model && q.check_model(m, "workspace_bytes")) return 0;
+  return q.bytes ? q.bytes(m, op) : carve(m, op, nullptr).total;
 }
 
 extern "C" int irlmx_execution_plan(const irlmx_mdp* mdp, int32_t op, int64_t* plan) {
   if (int rc = validate(mdp)) return rc;
   if (!plan) { set_error("plan is NULL"); return IRLMX_EINVAL; }
-  if (extended_op(op)) {
-    const Model m = make_model(mdp);
-    if (int rc = check_extended_op(m, op, "execution_plan")) return rc;
-    for (int i = 0; i < IRLMX_PLAN_LEN; ++i) plan[i] = 0;
-    extended_plan(m, plan);
-    return 0;
-  }
+  if (int rc = check_extended_flag(op)) return rc;
   // (a backward call with rescale = 0 never takes the cluster shape: see irlmx_backward_maxent)
-  const bool no_rescale = op > 0 && (op & IRLMX_PLAN_NO_RESCALE) != 0;
+  const bool no_rescale = op > 0 && !extended_op(op) && (op & IRLMX_PLAN_NO_RESCALE) != 0;
   if (no_rescale) op &= ~IRLMX_PLAN_NO_RESCALE;
-  // (IRLMX_OP_POLICY_EVALUATION is 6, the horizon ops 8 and 9 and the soft horizon op 11: the values
-  // between stay the unknown ops they have always been)
-  if (op < IRLMX_OP_BACKWARD || (op > IRLMX_OP_VALUE_ITERATION && op != IRLMX_OP_POLICY_EVALUATION && !horizon_op(op) &&
-                                 op != IRLMX_OP_SOFT_BACKWARD_HORIZON)) {
-    set_error("unknown op %d", op);
-    return IRLMX_EINVAL;
-  }
+  const OpQueries q = op_queries(op);
+  if (!q.known) { set_error("unknown op %d", op); return IRLMX_EINVAL; }
   if (no_rescale && op != IRLMX_OP_BACKWARD) { set_error("IRLMX_PLAN_NO_RESCALE applies to IRLMX_OP_BACKWARD only"); return IRLMX_EINVAL; }
   const Model m = make_model(mdp);
-  if (op == IRLMX_OP_POLICY_EVALUATION)
-    if (int rc = policy_eval_check_model(m, "execution_plan")) return rc;
-  for (int i = 0; i < IRLMX_PLAN_LEN; ++i) plan[i] = 0;
-  if (horizon_op(op)) {
-    if (int rc = horizon_check_model(m, "execution_plan")) return rc;
-    horizon_plan(m, op, plan);
-    return 0;
+  if (int rc = q.check_model ? q.check_model(m, "execution_plan") : 0) {
+    if (horizon_op(op)) std::fill_n(plan, IRLMX_PLAN_LEN, 0);  // (as these ops always have, although the model is refused)
+    return rc;
   }
-  if (op == IRLMX_OP_SOFT_BACKWARD_HORIZON) {
-    if (int rc = horizon_check_model(m, "execution_plan")) return rc;
-    soft_horizon_plan(m, plan);
+  std::fill_n(plan, IRLMX_PLAN_LEN, 0);
+  if (q.plan) {
+    q.plan(m, op, plan);
     return 0;
   }
   // (the compact layout is data-dependent: from the table's properties, else checked on the device)

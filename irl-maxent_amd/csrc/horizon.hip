@@ -35,11 +35,10 @@
 #include <hip/hip_runtime.h>
 
 #include "extended.h"
-#include "fixed_point.h"
+#include "horizon.h"
 
 namespace irlmx {
 
-constexpr int kHzMaxHorizon = 1 << 20;  // |e| grows by < 1100 per step: no int32 wrap
 constexpr int kHzRegActions = 4;        // actions of the register-resident table variant
 
 struct HzBwdArgs {
@@ -62,18 +61,6 @@ struct HzFwdArgs {
   double* svf_t;  // [B][T+1][S], may be null
   int32_t* status;
 };
-
-// per-sweep buffers (the fused kernels keep all of this in LDS)
-struct HzWs {
-  int32_t* bad;     // [B] backward: some exp(r) is non-finite
-  double* man[2];   // [B][S] backward mantissas / forward d_t, ping and pong
-  int32_t* exp[2];  // [B][S] backward exponents
-  size_t total;
-};
-
-__device__ inline size_t hz_pi_row(const Model& m, int T, int b, int t, int s) {
-  return (((size_t)b * T + t) * m.S + s) * m.A;
-}
 
 // log Z = e * ln 2 + log m; -inf for an exact zero
 __device__ inline double hz_log_z(double mant, int e) {
@@ -466,15 +453,11 @@ static void (*hz_fwd_fn(int spt))(HzFwdArgs) {
   return nullptr;
 }
 
-static size_t hz_fused_lds(const Model& m, int op) {
-  return (size_t)m.S * (op == IRLMX_OP_BACKWARD_HORIZON ? kExtLdsPerState : 2 * sizeof(double));
+size_t hz_fused_lds(const Model& m, int op) {
+  if (op == IRLMX_OP_BACKWARD_HORIZON) return (size_t)m.S * kExtLdsPerState;
+  return (op == IRLMX_OP_SOFT_BACKWARD_HORIZON ? sizeof(NpTables) : 0) + 2 * (size_t)m.S * sizeof(double);
 }
 
-// The fused shape of a horizon pass: the thread layout of the ordinary fused
-// backward / forward at every width (these passes have no cluster form), when
-// its pair is instantiated (fused_shape asks fused_pair_ok; the forward has no
-// slot classes), its LDS fits and (several states per thread) the batch is
-// large enough; else one launch per step.
 // Several states per thread (above 1,024 states) only from this many instances
 // on (IRLMX_HORIZON_FUSED_BATCH; tests use 1): one workgroup steps 4,096 states
 // in 24 us where a launch over 16 workgroups takes 11, so below one workgroup
@@ -487,14 +470,15 @@ int horizon_fused_min_batch() {
   return env_int("IRLMX_HORIZON_FUSED_BATCH", cus > 0 ? cus : 256);
 }
 
-static bool hz_fused_shape(const Model& m, int op, FusedShape* out) {
-  const bool bwd = op == IRLMX_OP_BACKWARD_HORIZON;
-  if (!fused_shape(m, bwd ? IRLMX_OP_BACKWARD : IRLMX_OP_FORWARD, out, false)) return false;
+bool hz_fused_shape(const Model& m, int op, FusedShape* out) {
+  // (the op whose fused_pair_ok list the kernels are instantiated from: the soft pass has its own)
+  const int pairs = op == IRLMX_OP_BACKWARD_HORIZON ? IRLMX_OP_BACKWARD : op == IRLMX_OP_FORWARD_HORIZON ? IRLMX_OP_FORWARD : op;
+  if (!fused_shape(m, pairs, out, false)) return false;
   if (out->spt > 1 && m.B < horizon_fused_min_batch()) return false;
   return hz_fused_lds(m, op) <= kExtLdsMax;
 }
 
-static HzWs hz_carve(const Model& m, int op, void* base) {
+HzWs hz_carve(const Model& m, int op, void* base) {
   HzWs w;
   Carver c{(char*)base};
   const size_t B = m.B, S = m.S;
@@ -521,15 +505,15 @@ size_t horizon_workspace_bytes(const Model& m, int op) { return hz_carve(m, op, 
 void horizon_plan(const Model& m, int op, int64_t* plan) {
   FusedShape fs;
   if (hz_fused_shape(m, op, &fs)) return plan_fused(plan, fs, hz_fused_lds(m, op));
-  plan_sweep(plan, 1, 0);  // one state per lane; the launch count is the horizon
+  plan_sweep(plan, 1, 0);  // one state per lane; the launch count is the horizon (the soft pass's: + 1)
 }
 
-static int hz_check_call(const Model& m, const char* fn, int op, int32_t horizon, size_t bytes, void* ws) {
+int hz_check_call(const Model& m, const char* fn, int op, int32_t horizon, size_t bytes, void* ws) {
   if (horizon < 1 || horizon > kHzMaxHorizon) {
     set_error("%s: horizon %d outside [1, %d]", fn, horizon, kHzMaxHorizon);
     return IRLMX_EINVAL;
   }
-  return check_ws(hz_carve(m, op, nullptr).total, bytes, ws);
+  return check_ws(horizon_workspace_bytes(m, op), bytes, ws);
 }
 
 }  // namespace irlmx
@@ -546,25 +530,18 @@ extern "C" int irlmx_backward_maxent_horizon(const irlmx_mdp* mdp, const double*
   if (int rc = need_all(fn, {{reward, "reward"}, {p_action_t, "p_action_t"}, {status, "status"}})) return rc;
   if (int rc = hz_check_call(m, fn, IRLMX_OP_BACKWARD_HORIZON, horizon, workspace_bytes, workspace)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  HzBwdArgs a{m, reward, terminal, horizon, p_action_t, log_z0, status};
-  FusedShape fs;
-  if (hz_fused_shape(m, IRLMX_OP_BACKWARD_HORIZON, &fs)) {
-    void (*kfn)(HzBwdArgs) = nullptr;
-    if (m.A <= kHzRegActions) kfn = hz_bwd_fn<true>(fs.spt, fs.kmax);
-    if (!kfn) kfn = hz_bwd_fn<false>(fs.spt, fs.kmax);
-    if (!kfn) { set_error("no horizon backward fused kernel for spt=%d kmax=%d", fs.spt, fs.kmax); return IRLMX_EINVAL; }
-    return launch_fused(kfn, "hz_bwd_fused_kernel", m.B, fs.threads, hz_fused_lds(m, IRLMX_OP_BACKWARD_HORIZON), st, a);
-  }
-  HzWs ws = hz_carve(m, IRLMX_OP_BACKWARD_HORIZON, workspace);
-  hipError_t e = hipMemsetAsync(ws.bad, 0, (size_t)m.B * sizeof(int32_t), st);
-  if (e != hipSuccess) return hip_fail(e, "workspace memset");
-  count_event(IRLMX_CTR_SWEEP_CALLS);
-  const dim3 g = sweep_grid(m);
-  hipLaunchKernelGGL(hz_bwd_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
-  for (int it = 0; it < horizon; ++it)
-    hipLaunchKernelGGL(hz_bwd_step_kernel, g, dim3(kSweepThreads), 0, st, a, ws, horizon - 1 - it, it & 1);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "horizon backward");
+  const HzBwdArgs a{m, reward, terminal, horizon, p_action_t, log_z0, status};
+  return hz_launch(
+      m, IRLMX_OP_BACKWARD_HORIZON, workspace, st, a, "horizon backward", "hz_bwd_fused_kernel",
+      [&](const FusedShape& fs) {
+        void (*kfn)(HzBwdArgs) = m.A <= kHzRegActions ? hz_bwd_fn<true>(fs.spt, fs.kmax) : nullptr;
+        return kfn ? kfn : hz_bwd_fn<false>(fs.spt, fs.kmax);
+      },
+      [&](const HzWs& ws) {
+        const hipError_t e = hipMemsetAsync(ws.bad, 0, (size_t)m.B * sizeof(int32_t), st);
+        if (e != hipSuccess) return hip_fail(e, "workspace memset");
+        return hz_launch_sweeps(m, hz_bwd_init_kernel, hz_bwd_step_kernel, a, ws, horizon, true, "horizon backward", st);
+      });
 }
 
 extern "C" int irlmx_forward_svf_horizon(const irlmx_mdp* mdp, const double* p_initial, const uint8_t* terminal,
@@ -579,19 +556,11 @@ extern "C" int irlmx_forward_svf_horizon(const irlmx_mdp* mdp, const double* p_i
     return rc;
   if (int rc = hz_check_call(m, fn, IRLMX_OP_FORWARD_HORIZON, horizon, workspace_bytes, workspace)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  HzFwdArgs a{m, p_initial, terminal, p_action_t, horizon, svf, svf_t, status};
-  FusedShape fs;
-  if (hz_fused_shape(m, IRLMX_OP_FORWARD_HORIZON, &fs)) {
-    void (*kfn)(HzFwdArgs) = hz_fwd_fn(fs.spt);
-    if (!kfn) { set_error("no horizon forward fused kernel for spt=%d", fs.spt); return IRLMX_EINVAL; }
-    return launch_fused(kfn, "hz_fwd_fused_kernel", m.B, fs.threads, hz_fused_lds(m, IRLMX_OP_FORWARD_HORIZON), st, a);
-  }
-  HzWs ws = hz_carve(m, IRLMX_OP_FORWARD_HORIZON, workspace);
-  count_event(IRLMX_CTR_SWEEP_CALLS);
-  const dim3 g = sweep_grid(m);
-  hipLaunchKernelGGL(hz_fwd_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
-  for (int t = 0; t < horizon; ++t)
-    hipLaunchKernelGGL(hz_fwd_step_kernel, g, dim3(kSweepThreads), 0, st, a, ws, t, t & 1);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "horizon forward");
+  const HzFwdArgs a{m, p_initial, terminal, p_action_t, horizon, svf, svf_t, status};
+  return hz_launch(
+      m, IRLMX_OP_FORWARD_HORIZON, workspace, st, a, "horizon forward", "hz_fwd_fused_kernel",
+      [&](const FusedShape& fs) { return hz_fwd_fn(fs.spt); },
+      [&](const HzWs& ws) {
+        return hz_launch_sweeps(m, hz_fwd_init_kernel, hz_fwd_step_kernel, a, ws, horizon, false, "horizon forward", st);
+      });
 }

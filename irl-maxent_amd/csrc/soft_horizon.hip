@@ -24,11 +24,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "fixed_point.h"
+#include "horizon.h"
 
 namespace irlmx {
-
-constexpr int kShMaxHorizon = 1 << 20;
 
 struct SoftHzArgs {
   Model m;
@@ -41,15 +39,11 @@ struct SoftHzArgs {
   int32_t* status;
 };
 
-// per-sweep buffers (the fused kernel keeps V in LDS)
+// per-sweep buffers (the fused kernel keeps V in LDS): hz_carve's man[0..1]
 struct ShWs {
   double* v[2];  // [B][S] ping and pong
   size_t total;
 };
-
-__device__ inline size_t sh_pi_row(const Model& m, int T, int b, int t, int s) {
-  return (((size_t)b * T + t) * m.S + s) * m.A;
-}
 
 // One state of one step: writes the policy row `out`, returns v (step 2).
 // KMAX > 0: the slot class is compiled in, and up to 8 slots the slot loop is
@@ -130,7 +124,7 @@ __global__ void __launch_bounds__(1024) soft_hz_fused_kernel(SoftHzArgs a) {
     const double* vin = (it & 1) ? vB : vA;
     double* vout = (it & 1) ? vA : vB;
     auto state = [&](int s, double rs, bool ts, auto&& nbr) __attribute__((always_inline)) {
-      double v = sh_row<KMAX>(m, b, s, rs, a.discount, vin, nbr, tabs, a.pi + sh_pi_row(m, T, b, t, s));
+      double v = sh_row<KMAX>(m, b, s, rs, a.discount, vin, nbr, tabs, a.pi + hz_pi_row(m, T, b, t, s));
       if (ts) v = rs;  // absorbing: V_t = r, held
       vout[s] = v;
       if (t == 0) {
@@ -179,7 +173,7 @@ __global__ void __launch_bounds__(kSweepThreads) soft_hz_step_kernel(SoftHzArgs 
   const double r = a.reward[i];
   double v = sh_row<0>(m, b, s, r, a.discount, ws.v[odd] + (size_t)b * S,
                        [&](int k) __attribute__((always_inline)) { return row_nbr(m, b, s, k); }, &kNpTabs,
-                       a.pi + sh_pi_row(m, a.T, b, t, s));
+                       a.pi + hz_pi_row(m, a.T, b, t, s));
   if (a.term && a.term[i]) v = r;
   ws.v[odd ^ 1][i] = v;
   if (t == 0) {
@@ -201,35 +195,6 @@ static void (*soft_hz_fn(int spt, int kmax))(SoftHzArgs) {
   });
 }
 
-// the NpTables copy, then V ping and pong: 16 B per state
-static size_t soft_hz_fused_lds(const Model& m) { return sizeof(NpTables) + 2 * (size_t)m.S * sizeof(double); }
-
-// The fused shape of the pass: the non-causal horizon backward's rule
-// (horizon_fused_min_batch: several states per thread only from one workgroup
-// per CU on), over this pass's own pair list.
-static bool soft_hz_fused_shape(const Model& m, FusedShape* out) {
-  if (!fused_shape(m, IRLMX_OP_SOFT_BACKWARD_HORIZON, out, false)) return false;
-  return out->spt == 1 || m.B >= horizon_fused_min_batch();
-}
-
-static ShWs soft_hz_carve(const Model& m, void* base) {
-  ShWs w;
-  Carver c{(char*)base};
-  FusedShape fs;
-  const bool sweep = !soft_hz_fused_shape(m, &fs);
-  for (int i = 0; i < 2; ++i) w.v[i] = c.take<double>(sweep ? (size_t)m.B * m.S * sizeof(double) : 0);
-  w.total = c.total();
-  return w;
-}
-
-size_t soft_horizon_workspace_bytes(const Model& m) { return soft_hz_carve(m, nullptr).total; }
-
-void soft_horizon_plan(const Model& m, int64_t* plan) {
-  FusedShape fs;
-  if (soft_hz_fused_shape(m, &fs)) return plan_fused(plan, fs, soft_hz_fused_lds(m));
-  plan_sweep(plan, 1, 0);  // one state per lane; the launch count is the horizon + 1
-}
-
 }  // namespace irlmx
 
 using namespace irlmx;
@@ -246,25 +211,15 @@ extern "C" int irlmx_soft_backward_horizon(const irlmx_mdp* mdp, const double* r
     set_error("%s: discount %g outside [0, 1]", fn, discount);
     return IRLMX_EINVAL;
   }
-  if (horizon < 1 || horizon > kShMaxHorizon) {
-    set_error("%s: horizon %d outside [1, %d]", fn, horizon, kShMaxHorizon);
-    return IRLMX_EINVAL;
-  }
-  if (int rc = check_ws(soft_hz_carve(m, nullptr).total, workspace_bytes, workspace)) return rc;
+  if (int rc = hz_check_call(m, fn, IRLMX_OP_SOFT_BACKWARD_HORIZON, horizon, workspace_bytes, workspace)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  SoftHzArgs a{m, reward, terminal, discount, horizon, p_action_t, value0, status};
-  FusedShape fs;
-  if (soft_hz_fused_shape(m, &fs)) {
-    void (*kfn)(SoftHzArgs) = soft_hz_fn(fs.spt, fs.kmax);
-    if (!kfn) { set_error("no soft horizon fused kernel for spt=%d kmax=%d", fs.spt, fs.kmax); return IRLMX_EINVAL; }
-    return launch_fused(kfn, "soft_hz_fused_kernel", m.B, fs.threads, soft_hz_fused_lds(m), st, a);
-  }
-  const ShWs ws = soft_hz_carve(m, workspace);
-  count_event(IRLMX_CTR_SWEEP_CALLS);
-  const dim3 g = sweep_grid(m);
-  hipLaunchKernelGGL(soft_hz_init_kernel, g, dim3(kSweepThreads), 0, st, a, ws);
-  for (int it = 0; it < horizon; ++it)
-    hipLaunchKernelGGL(soft_hz_step_kernel, g, dim3(kSweepThreads), 0, st, a, ws, horizon - 1 - it, it & 1);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "soft horizon backward");
+  const SoftHzArgs a{m, reward, terminal, discount, horizon, p_action_t, value0, status};
+  return hz_launch(
+      m, IRLMX_OP_SOFT_BACKWARD_HORIZON, workspace, st, a, "soft horizon backward", "soft_hz_fused_kernel",
+      [&](const FusedShape& fs) { return soft_hz_fn(fs.spt, fs.kmax); },
+      [&](const HzWs& w) {
+        const ShWs ws{{w.man[0], w.man[1]}, w.total};
+        return hz_launch_sweeps(m, soft_hz_init_kernel, soft_hz_step_kernel, a, ws, horizon, true,
+                                "soft horizon backward", st);
+      });
 }

@@ -68,7 +68,7 @@ MaxCausalEnt model, for stochastic dynamics.
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .mdp import DeviceMDP
 from .optim import ExpSga, linear_decay
 
@@ -108,7 +108,7 @@ class BatchedMaxEnt:
             if causal:
                 raise ValueError("horizon applies to the non-causal model only (the finite-horizon causal model "
                                  "is BatchedCausalHorizon)")
-            if int(horizon) != horizon or not 1 <= int(horizon) <= (1 << 20):
+            if int(horizon) != horizon or not 1 <= int(horizon) <= _lib.HORIZON_MAX:
                 raise ValueError(f"horizon must be an integer in [1, 2^20], got {horizon!r}")
             horizon = int(horizon)
         self.horizon = horizon

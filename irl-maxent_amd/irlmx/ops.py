@@ -333,6 +333,13 @@ def _optional_mask(terminal, mdp):
     return terminal.to(device=mdp.device, dtype=torch.uint8).reshape(mdp.batch, mdp.n_states).contiguous()
 
 
+def _horizon_policy(mdp, horizon):
+    """``(T, uninitialised pi_t [B, T, S, A])``; for a T outside [1, HORIZON_MAX] the call raises: one step is allocated."""
+    T = int(horizon)
+    shape = (mdp.batch, T if 1 <= T <= _lib.HORIZON_MAX else 1, mdp.n_states, mdp.n_actions)
+    return T, torch.empty(shape, dtype=torch.float64, device=mdp.device)
+
+
 def backward_maxent_horizon(mdp, reward, horizon, terminal=None, return_log_z0=False):
     """Time-indexed local action probabilities ``pi_t`` [B, T, S, A] of the
     finite-horizon MaxEnt model with ``T = horizon`` steps
@@ -349,11 +356,10 @@ def backward_maxent_horizon(mdp, reward, horizon, terminal=None, return_log_z0=F
     instance at T = 128.  STENCIL5 and ELL models; ``execution_plan(mdp,
     "backward_horizon")`` names the shape."""
     lib = _lib.load()
-    B, S, A, T = mdp.batch, mdp.n_states, mdp.n_actions, int(horizon)
+    B, S = mdp.batch, mdp.n_states
     r = _f64(reward, mdp, (B, S))
     term = _optional_mask(terminal, mdp)
-    ok = 1 <= T <= _lib.HORIZON_MAX      # (else the call below raises: nothing of size T is allocated)
-    pi = torch.empty((B, T if ok else 1, S, A), dtype=torch.float64, device=mdp.device)
+    T, pi = _horizon_policy(mdp, horizon)
     lz = torch.empty((B, S), dtype=torch.float64, device=mdp.device) if return_log_z0 else None
     status = torch.empty(B, dtype=torch.int32, device=mdp.device)
     ws, n = _workspace(mdp, _lib.OP_BACKWARD_HORIZON)
@@ -378,11 +384,10 @@ def soft_backward_horizon(mdp, reward, discount, horizon, terminal=None, return_
     Memory: the result is ``B * T * S * A * 8`` bytes.  STENCIL5 and ELL models;
     ``execution_plan(mdp, "soft_backward_horizon")`` names the shape."""
     lib = _lib.load()
-    B, S, A, T = mdp.batch, mdp.n_states, mdp.n_actions, int(horizon)
+    B, S = mdp.batch, mdp.n_states
     r = _f64(reward, mdp, (B, S))
     term = _optional_mask(terminal, mdp)
-    ok = 1 <= T <= _lib.HORIZON_MAX      # (else the call below raises: nothing of size T is allocated)
-    pi = torch.empty((B, T if ok else 1, S, A), dtype=torch.float64, device=mdp.device)
+    T, pi = _horizon_policy(mdp, horizon)
     v0 = torch.empty((B, S), dtype=torch.float64, device=mdp.device) if return_value0 else None
     status = torch.empty(B, dtype=torch.int32, device=mdp.device)
     ws, n = _workspace(mdp, _lib.OP_SOFT_BACKWARD_HORIZON)

@@ -324,6 +324,23 @@ def forward_svf_horizon(mdp, p_initial, p_action_t, terminal=None, svf_t=True, f
     return _run("irlmx_forward_svf_horizon", mdp, _lib.OP_FORWARD_HORIZON, out, call, fill, donor)
 
 
+def soft_backward_horizon(mdp, reward, discount, horizon, terminal=None, value0=True, fill="zero", donor=None):
+    """irlmx_soft_backward_horizon: {"p_action_t" [B, T, S, A], "value0" [B, S] or None (``value0=False``: NULL),
+    "status"}.  ``donor``: ``reward``."""
+    from irlmx import _lib
+    B, S, A, T, dev = mdp.batch, mdp.n_states, mdp.n_actions, int(horizon), mdp.device
+    out = {"p_action_t": _out(torch.float64, (B, T, S, A), dev), "value0": _out(torch.float64, (B, S), dev, value0),
+           "status": _out(torch.int32, (B,), dev)}
+
+    def call(lib, ws, n, st, reward=reward):
+        r, tm = _in(reward, torch.float64, (B, S), dev), _in(terminal, torch.uint8, (B, S), dev)
+        return lib.irlmx_soft_backward_horizon(mdp.struct(), _lib.ptr(r), _lib.ptr(tm), float(discount), T,
+                                               _lib.ptr(out["p_action_t"]), _lib.ptr(out["value0"]),
+                                               _lib.ptr(out["status"]), ws, n, st), (r, tm)
+
+    return _run("irlmx_soft_backward_horizon", mdp, _lib.OP_SOFT_BACKWARD_HORIZON, out, call, fill, donor)
+
+
 #: C name -> the function above that calls it: every entry point of include/irlmx.h with a
 #: ``void* workspace`` parameter (tests/test_call_contract_host.py holds the two sets equal)
 WRAPPED = {
@@ -335,4 +352,5 @@ WRAPPED = {
     "irlmx_policy_evaluation": policy_evaluation,
     "irlmx_backward_maxent_horizon": backward_maxent_horizon,
     "irlmx_forward_svf_horizon": forward_svf_horizon,
+    "irlmx_soft_backward_horizon": soft_backward_horizon,
 }

@@ -71,22 +71,6 @@ def test_symbol_exported_and_bound(lib):
     assert lib.irlmx_abi_version() == 1
 
 
-def test_entry_is_wrapped_for_the_call_contract():
-    """tests/abi_call.py's table is closed (tests/test_call_contract_host.py pins its eight ``void* workspace``
-    entry points); this entry's workspace pointer is declared ``void* workspace_mem`` and every such
-    declaration has its wrapper in tests/soft_horizon_call.py."""
-    import os
-    import abi_call as A
-    import soft_horizon_call as SC
-    from irlmx import _lib
-    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "irlmx.h")
-    declared = SC.declared_with_workspace_mem(header)
-    assert declared == set(SC.WRAPPED) == {"irlmx_soft_backward_horizon"}, declared
-    assert not set(SC.WRAPPED) & set(A.WRAPPED)
-    for name, fn in SC.WRAPPED.items():
-        assert name in _lib.SIGNATURES and callable(fn) and "irlmx_" + fn.__name__ == name, name
-
-
 def test_null_arguments(lib):
     assert call(lib, None) == EINVAL and err(lib) == "mdp is NULL"
     for name in ("reward", "p_action_t", "status"):

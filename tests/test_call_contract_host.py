@@ -41,7 +41,8 @@ def declared_with_workspace():
 
 def test_every_entry_point_with_a_workspace_is_wrapped():
     declared = declared_with_workspace()
-    assert len(declared) == 8 and "irlmx_forward_svf_horizon" in declared, declared   # the parser sees them
+    assert len(declared) == 9 and "irlmx_forward_svf_horizon" in declared, declared   # the parser sees them
+    assert "irlmx_soft_backward_horizon" in declared, declared
     assert declared == set(A.WRAPPED), (declared - set(A.WRAPPED), set(A.WRAPPED) - declared)
     from irlmx import _lib
     for name, fn in A.WRAPPED.items():
@@ -177,7 +178,7 @@ def test_workspace_bytes_are_multiples_of_256(lib, monkeypatch):
     ops = {"backward": _lib.OP_BACKWARD, "extended": _lib.OP_BACKWARD | _lib.PLAN_EXTENDED_RANGE,
            "forward": _lib.OP_FORWARD, "soft": _lib.OP_SOFT_BACKWARD, "vi": _lib.OP_VALUE_ITERATION,
            "policy evaluation": _lib.OP_POLICY_EVALUATION, "backward horizon": _lib.OP_BACKWARD_HORIZON,
-           "forward horizon": _lib.OP_FORWARD_HORIZON}
+           "forward horizon": _lib.OP_FORWARD_HORIZON, "soft backward horizon": _lib.OP_SOFT_BACKWARD_HORIZON}
     positive = 0
     for name, (dims, envs) in G.MODELS.items():
         m = _lib.MDPStruct()
@@ -194,7 +195,8 @@ def test_workspace_bytes_are_multiples_of_256(lib, monkeypatch):
             for what, op in ops.items():
                 n = int(lib.irlmx_workspace_bytes(ctypes.byref(m), op))
                 assert n % 256 == 0, (name, keys, what, n)
-                if dims[0] == G.DENSE and what in ("extended", "policy evaluation", "backward horizon", "forward horizon"):
+                if dims[0] == G.DENSE and what in ("extended", "policy evaluation", "backward horizon", "forward horizon",
+                                                    "soft backward horizon"):
                     assert n == 0, (name, what, n)             # not run on the DENSE layout
                 elif "horizon" not in what:
                     assert n > 0, (name, keys, what, n)        # (the fused horizon shapes need none)

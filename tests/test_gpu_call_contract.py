@@ -74,6 +74,9 @@ irlmx_backward_maxent_horizon / irlmx_forward_svf_horizon (hz_carve(), horizon.h
   bad     backward: hipMemsetAsync(ws.bad) in the entry point, atomicOr in hz_bwd_init_kernel
   man[0], exp[0]   hz_bwd_init_kernel / hz_fwd_init_kernel (the forward has no exp)
   man[1], exp[1]   the first hz_*_step_kernel, before the second reads them
+  irlmx_soft_backward_horizon (the same hz_carve(): man[0..1] alone, as the forward; its kernels' v[0..1]):
+  v[0]    soft_hz_init_kernel writes all of it
+  v[1]    the first soft_hz_step_kernel, before the second reads it
 
 irlmx_policy_evaluation (carve(), fixed_point.hip; policy_eval.hip):
   wgt     pe_weights_kernel writes all of it; read by pe_fused_kernel / pe_sweep_kernel
@@ -430,6 +433,43 @@ def test_per_sweep_by_slot_count(dev, env, family):
         policy_eval("k40-s300", dev, "sweep")
     else:
         horizon("k40-s300", dev, "sweep", "sweep")
+
+
+# ---------------------------------------------------------------------------
+# finite-horizon soft value iteration, fused and per sweep
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("shape", ["fused", "sweep"])
+@pytest.mark.parametrize("name,discount", [("16x16", 1.0), ("37x23", 0.9), ("k8-s1029", 0.9)])
+def test_soft_backward_horizon_contract(dev, env, name, discount, shape):
+    """irlmx_soft_backward_horizon on both shapes, with value0 given and NULL:
+    ``ops.soft_backward_horizon``'s bits whatever the workspace held -- the
+    donor's rewards hold a NaN -- and no output entry keeps its sentinel, the
+    NONFINITE instance's included."""
+    from irlmx import _lib, ops
+    env(NO_FUSED if shape == "sweep" else {"IRLMX_HORIZON_FUSED_BATCH": 1})    # several states per thread fused at any batch
+    c = H.case(name)
+    mdp = c.device_model(dev)
+    plan = ops.execution_plan(mdp, "soft_backward_horizon")
+    assert plan["shape"] == shape, plan
+    need = int(_lib.load().irlmx_workspace_bytes(mdp.struct(), _lib.OP_SOFT_BACKWARD_HORIZON))
+    assert need == (0 if shape == "fused" else 2 * (-(-c.B * c.S * 8 // 256) * 256)), need   # each buffer 256-aligned
+    tm = ops.terminal_mask(c.terminal, c.S, batch=c.B, device=dev) if c.terminal else None
+    reward = np.array(c.reward)
+    pi, v0 = ops.soft_backward_horizon(mdp, reward, discount, c.T, tm, return_value0=True)
+    donor = {"reward": other_reward(reward)}
+    with_v0 = contract(f"{name}/{shape} soft horizon", lambda **kw: A.soft_backward_horizon(
+        mdp, reward, discount, c.T, tm, **kw), donor, {"p_action_t": pi, "value0": v0})
+    assert with_v0["status"].tolist() == [_lib.OK] * c.B
+    without = contract(f"{name}/{shape} soft horizon, value0 NULL", lambda **kw: A.soft_backward_horizon(
+        mdp, reward, discount, c.T, tm, value0=False, **kw), donor, {"p_action_t": pi})
+    assert without["value0"] is None and without["status"].tolist() == [_lib.OK] * c.B
+    # a NONFINITE instance: every entry written all the same, and the status computed without value0
+    bad = donor["reward"]
+    for value0 in (True, False):
+        got = contract(f"{name}/{shape} soft horizon, NaN reward", lambda **kw: A.soft_backward_horizon(
+            mdp, bad, discount, c.T, tm, value0=value0, **kw), {"reward": reward}, {})
+        assert got["status"].tolist() == [_lib.OK] * (c.B - 1) + [_lib.NONFINITE], got["status"]
 
 
 # ---------------------------------------------------------------------------
