@@ -252,6 +252,65 @@ __device__ inline int code_exponent(unsigned c) {
   return (c == 0u || c == kCodeNonFinite) ? 0 : -((int)c - (int)kCodeBias);
 }
 
+// The hand-off of a plan whose granule offsets are one per-thread base plus
+// wave-uniform terms (cluster.hip, config 3's trapezoid plan): the base is a
+// loop-invariant VGPR, the parity and the row terms travel in the buffer
+// instruction's scalar offset, so a block spends no vector arithmetic on
+// addresses.  Same granules, tags and store forms as gran_store / gran_gather.
+template <bool PLAIN>
+__device__ inline void gran_store_at(const Gran& g, unsigned voff, unsigned soff, unsigned long long v, unsigned tag) {
+  if (!IRLMX_DCHECK(gran_in(g, voff + soff), kCheckGranule)) return;
+  const u32x4 x = {(unsigned)v, tag, (unsigned)(v >> 32), tag};
+  __builtin_amdgcn_raw_buffer_store_b128(x, g.r, (int)voff, (int)soff, PLAIN ? 0 : 16 /* sc1 */);
+}
+// gran_gather for a tile's two sides of two granules each (voff + s_up, + s_half;
+// voff + s_dn, + s_half; `up` / `dn` wave-uniform: the tile has that neighbour)
+// and one summary granule: a pass loads every granule the lane asked for, with
+// no per-granule state -- a lane that misses one re-reads all of its own (a
+// granule keeps its tag until its writer has read this tile's next block).
+__device__ inline bool gran_gather_sides(const Gran& r, const Gran& rs, unsigned voff, unsigned s_up, unsigned s_dn,
+                                         unsigned s_half, bool up, bool dn, unsigned off_sum, bool want_sum,
+                                         unsigned tag, unsigned long long (&v)[4], unsigned long long& vsum,
+                                         unsigned long long limit, unsigned long long* passes) {
+#if IRLMX_DEVICE_CHECKS
+  if (up && !IRLMX_DCHECK(gran_in(r, voff + s_up + s_half), kCheckGranule)) return false;
+  if (dn && !IRLMX_DCHECK(gran_in(r, voff + s_dn + s_half), kCheckGranule)) return false;
+  if (want_sum && !IRLMX_DCHECK(gran_in(rs, off_sum), kCheckGranule)) return false;
+#endif
+  u32x4 x0, x1, x2, x3, xs;
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  bool miss;
+  for (;;) {
+    if (up) {
+      x0 = __builtin_amdgcn_raw_buffer_load_b128(r.r, (int)voff, (int)s_up, 16 /* sc1 */);
+      x1 = __builtin_amdgcn_raw_buffer_load_b128(r.r, (int)voff, (int)(s_up + s_half), 16);
+    }
+    if (dn) {
+      x2 = __builtin_amdgcn_raw_buffer_load_b128(r.r, (int)voff, (int)s_dn, 16);
+      x3 = __builtin_amdgcn_raw_buffer_load_b128(r.r, (int)voff, (int)(s_dn + s_half), 16);
+    }
+    if (want_sum) xs = __builtin_amdgcn_raw_buffer_load_b128(rs.r, (int)off_sum, 0, 16);
+    if (passes) *passes += 1ull;  // (while the loads are in flight)
+    miss = false;
+    if (up) miss |= (x0.y != tag) | (x0.w != tag) | (x1.y != tag) | (x1.w != tag);
+    if (dn) miss |= (x2.y != tag) | (x2.w != tag) | (x3.y != tag) | (x3.w != tag);
+    if (want_sum) miss |= (xs.y != tag) | (xs.w != tag);
+    if (!miss) break;
+    if (__builtin_amdgcn_s_memrealtime() - t0 > limit) break;  // timed out
+    __builtin_amdgcn_s_sleep(kPollSleep);
+  }
+  if (up) {
+    v[0] = ((unsigned long long)x0.z << 32) | x0.x;
+    v[1] = ((unsigned long long)x1.z << 32) | x1.x;
+  }
+  if (dn) {
+    v[2] = ((unsigned long long)x2.z << 32) | x2.x;
+    v[3] = ((unsigned long long)x3.z << 32) | x3.x;
+  }
+  if (want_sum) vsum = ((unsigned long long)xs.z << 32) | xs.x;
+  return !miss;
+}
+
 // cluster_run's result when a forward instance turned non-finite: the call must
 // be rerun on the per-sweep shape (exact NaN bookkeeping; cluster.hip)
 constexpr int kClusterNonFinite = 1;

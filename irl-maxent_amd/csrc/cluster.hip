@@ -969,6 +969,77 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
       else go(std::false_type{});
     }
   };
+  // Hand-off of the trapezoid plan (kTrap && trap: width 128, R 32, G 8, 512
+  // threads, tiles of exactly 32 rows) with the plan's constants compiled in.
+  // The granules, tags, parities, summary slots and who waits for whom are the
+  // generic code's (the block loop below); what differs is how a thread gets
+  // at its granules:
+  //  * a side is 8 rows = 1024 granules, and thread t publishes and polls
+  //    granules t and t + 512 of each side.  Every offset is then hoff (per
+  //    thread, the same in every block) plus a wave-uniform term -- parity,
+  //    side, + 8 KiB -- that travels in the buffer instruction's scalar offset;
+  //    the LDS addresses are one base plus constants;
+  //  * an edge tile publishes only the side that has a reader;
+  //  * the staged values are read from LDS before the first store (the
+  //    generic loop waits out one LDS round trip per granule), and the store
+  //    form (plain / write-through) is chosen once, around straight-line stores;
+  //  * a polling pass loads every granule the thread waits for, back to back
+  //    behind two wave-uniform branches (the tile has an upper / a lower
+  //    neighbour), and keeps no per-granule state: a thread that misses one
+  //    re-reads all of its own (gran_gather_sides); the ghosts then go to LDS
+  //    behind the same two branches, not one exec-mask branch per granule.
+  // Measured at config 3 (profiles/handoff_ab.txt): 19.7 -> 18.3 ms per call,
+  // 0.6 ms from the publication and 0.8 ms from the gather.  Storing the summary
+  // granule only in the blocks that poll summaries measured within the spread
+  // and is not done: every block stores it, as before.
+  const unsigned hoff = ((unsigned)e0 * 128u + (unsigned)tid) * 16u;  // this thread's first upper ghost granule, parity 0
+  const bool has_up = tile > 0, has_dn = tile + 1 < a.C;
+  auto trap_publish = [&](const int m, const unsigned tag, const unsigned gpar, const unsigned* red32) {
+    if constexpr (kTrap) {
+      constexpr int kLow = (kTrapR - kTrapT) * 128;  // first state of the lower side, from the first owned state
+      const double* p = bufA + pad + own0 + tid;
+      const double a0 = p[0], a1 = p[NT], b0 = p[kLow], b1 = p[kLow + NT];
+      const unsigned sA = (unsigned)__builtin_amdgcn_readfirstlane((int)((gpar + (unsigned)own0) * 16u));
+      const unsigned sB = sA + kLow * 16u;
+      auto go = [&](auto ptag) {
+        constexpr bool kPlain = decltype(ptag)::value;
+        if (tid == 0)
+          gran_store(rs, ((unsigned)(m % kSumSlots) * (unsigned)a.H + (unsigned)tile) * 16u, red32[m & 1], tag, kPlain);
+        if (has_up) {
+          gran_store_at<kPlain>(rg, hoff, sA, dbits(a0), tag);
+          gran_store_at<kPlain>(rg, hoff, sA + NT * 16u, dbits(a1), tag);
+        }
+        if (has_dn) {
+          gran_store_at<kPlain>(rg, hoff, sB, dbits(b0), tag);
+          gran_store_at<kPlain>(rg, hoff, sB + NT * 16u, dbits(b1), tag);
+        }
+      };
+      if (plain) go(std::true_type{});
+      else go(std::false_type{});
+    }
+  };
+  auto trap_gather = [&](const int m, const unsigned tag, const unsigned gpar, unsigned* red32, const bool need_sum) {
+    bool got = true;
+    if constexpr (kTrap) {
+      const unsigned sU = (unsigned)__builtin_amdgcn_readfirstlane((int)(gpar * 16u));
+      const unsigned sL = (unsigned)__builtin_amdgcn_readfirstlane((int)((gpar + (unsigned)own1) * 16u));
+      const bool pend_sum = need_sum && tid < a.C;
+      const unsigned off_sum = ((unsigned)(m % kSumSlots) * (unsigned)a.H + (unsigned)tid) * 16u;
+      unsigned long long v[4], vsum = 0ull;
+      got = gran_gather_sides(rg, rs, hoff, sU, sL, NT * 16u, has_up, has_dn, off_sum, pend_sum, tag, v, vsum,
+                              a.gather_ticks, stamps ? &st_acc[9] : nullptr);
+      double* q = bufA + pad + tid;
+      if (has_up) { q[0] = bits_double(v[0]); q[NT] = bits_double(v[1]); }
+      if (has_dn) { q[own1] = bits_double(v[2]); q[own1 + NT] = bits_double(v[3]); }
+      if (pend_sum) atomicMax(&red32[2 + (m & 1)], (unsigned)vsum);
+      if (stamps) {  // st_acc[9]: this block's passes
+        st_acc[7] += st_acc[9];
+        if (st_acc[9] > st_acc[8]) st_acc[8] = st_acc[9];
+        st_acc[9] = 0ull;
+      }
+    }
+    return got;
+  };
   for (int m = 0;; ++m) {
     int Tm = T;
     if (MODE == kModeBwd) Tm = (int)min<long long>((long long)T, total - done);
@@ -1086,7 +1157,9 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     }
     if (stamps) { const unsigned long long t = stamp_now(); st_acc[6] += t - ts; }
     __syncthreads();  // the tile summary in red32[m & 1] (and COLS: the staged rows) complete
-    if (!solo) {
+    if (kTrap && trap) {
+      if constexpr (kTrap) trap_publish(m, tag, gpar, red32);
+    } else if (!solo) {
       if (tid == 0) gran_store(rs, ((unsigned)(m % kSumSlots) * (unsigned)a.H + (unsigned)tile) * 16u, red32[m & 1], tag, plain);
       if constexpr (COLS && CPL == 2) {
         store_rows();
@@ -1159,8 +1232,13 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
         st_acc[9] = 0ull;
       }
     };
-    if (!solo) gather();
-    else if (tid == 0) red32[2 + (m & 1)] = red32[m & 1];
+    if (kTrap && trap) {
+      if constexpr (kTrap) ok = trap_gather(m, tag, gpar, red32, need_summary);
+    } else if (!solo) {
+      gather();
+    } else if (tid == 0) {
+      red32[2 + (m & 1)] = red32[m & 1];
+    }
     if (!ok) { lflag[0] = 1; atomicOr(a.err, 1); }
     __syncthreads();
     if (lflag[0]) return;  // exchange timed out (reported through a.err)
@@ -1302,6 +1380,9 @@ __global__ void __launch_bounds__(NT) cluster_kernel(ClusterArgs a) {
     // alternations on one box): one 128x128 instance's forward 14.53 -> 14.17 ms
     // per 20,000 sweeps without this barrier, but config 3's backward 22.50 ->
     // 22.77 ms -- so only the forward drops it.
+    // (Re-measured for the trapezoid plan's hand-off, profiles/handoff_ab.txt:
+    // 0.12-0.18 ms of 18.3 faster without it in three A/Bs, but only one of them
+    // by three times the spread of the medians, so it stays.)
     if constexpr (!COLS || CW || MODE == kModeBwd) __syncthreads();
     stamp(3);
     if (MODE == kModeBwd && done >= total) break;
