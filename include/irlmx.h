@@ -189,6 +189,50 @@ int irlmx_numpy_math(int32_t op, const double* x, double* y, int64_t n, void* st
  *    (an optional output that is given -- value, log_z0, svf_t, value0 -- likewise).
  *    No output entry is read before it is written: outputs may be
  *    uninitialised memory.
+ *
+ * Stream order, of every entry point that takes `stream` (with or without a
+ * workspace; tests/test_gpu_stream_order.py holds each of them to it on a
+ * non-blocking side stream, behind a device delay, with inputs that land
+ * late):
+ *  - Everything a call enqueues -- kernels, memsets, copies, stream-ordered
+ *    allocations -- goes to `stream`, and a value the host reads back is read
+ *    after a synchronise of `stream`.  Nothing goes to the default stream.
+ *  - Inputs, workspace and outputs need only be valid in stream order: the
+ *    work that produces an input may still be pending on `stream` when the call
+ *    is made, and an input buffer may be overwritten by later work on `stream`
+ *    as soon as the call has returned.  (The irlmx_mdp struct itself, and
+ *    props, are host memory read during the call.)
+ *  - Two calls on two streams, each with its own workspace and outputs, may be
+ *    in flight together; each returns the bits it returns alone.
+ *  - Whether a call may synchronise `stream` (block the host until the work
+ *    queued on it, the call's own included, has run) depends on the entry point
+ *    and the shape irlmx_execution_plan names.  "asynchronous" calls neither
+ *    synchronise, nor allocate, nor wait for the device in any other way:
+ *      fused shape of every pass                                asynchronous
+ *      irlmx_backward_maxent: per sweep, DENSE streaming
+ *        and DENSE GEMM (2*S - 1 sweeps, no host read)          asynchronous
+ *      irlmx_backward_maxent_extended per sweep                 asynchronous
+ *      the three *_horizon passes, both shapes                  asynchronous
+ *      irlmx_rollout, irlmx_demo_statistics,
+ *        irlmx_demo_log_likelihood, irlmx_numpy_math            asynchronous
+ *      the four *_numpy_order calls: STENCIL5 and DENSE
+ *        models, ELL models with props set                      asynchronous
+ *        (ELL with props 0: the row-order check synchronises)
+ *      irlmx_optimal_policy, irlmx_stochastic_policy,
+ *        irlmx_build_icy_gridworld, irlmx_build_gridworld,
+ *        irlmx_dense_to_stencil, irlmx_dense_to_rows,
+ *        irlmx_dense_ell_sizes, irlmx_dense_to_ell,
+ *        irlmx_dense_gemm                                       asynchronous
+ *      irlmx_forward_svf, irlmx_soft_backward,
+ *        irlmx_value_iteration, irlmx_policy_evaluation on
+ *        the per-sweep, DENSE streaming and DENSE GEMM shapes
+ *        (the host polls the done counter every chunk of
+ *        sweeps)                                                may synchronise
+ *      the cluster, grid and dense-grid shapes of every pass,
+ *        the grid shape of irlmx_backward_maxent_extended
+ *        (each launch's outcome is read on the host)            may synchronise
+ *      irlmx_mdp_properties; a width-256 STENCIL5 backward
+ *        or its plan with props 0                               synchronises
  */
 size_t irlmx_workspace_bytes(const irlmx_mdp* mdp, int32_t op);
 

@@ -22,7 +22,16 @@ hold each call to what include/irlmx.h states beside irlmx_workspace_bytes:
 A broken promise raises ContractViolation.  ``contract_call`` and the classes
 below do not care which device their tensors are on:
 tests/test_call_contract_host.py runs them against stand-in calls on the CPU.
+
+Stream order (``stream_call``, and ``side=`` of every function below): the same
+call on a non-blocking side stream, behind a device delay, with inputs that
+land late -- see ``Side``.  tests/test_gpu_stream_order.py runs every entry
+point of the header that takes a ``stream`` through it.
 """
+
+import ctypes
+import inspect
+import time
 
 import numpy as np
 import torch
@@ -162,6 +171,114 @@ def contract_call(what, device, n, outputs, invoke, fill="zero", donor=None):
 
 
 # ---------------------------------------------------------------------------
+# the same call on a side stream, behind a delay
+# ---------------------------------------------------------------------------
+
+class HarnessDrained(AssertionError):
+    """The delay had run out before the entry point was called: the set-up blocked
+    the host or the delay is too short.  A defect of the test, not of the library."""
+
+
+class AsynchronyViolation(AssertionError):
+    """A call declared asynchronous returned only after the work queued before it had run."""
+
+
+class Side:
+    """How ``stream_call`` runs one call: on ``stream`` (a torch.cuda.Stream, which
+    is non-blocking: it does not wait for the legacy default stream; None: the
+    current stream), behind
+    ``cycles`` of ``torch.cuda._sleep`` (0: no delay), the workspace filled with
+    ``fill`` in stream order.  ``claim`` "async": the call must return while the
+    delay still runs (AsynchronyViolation otherwise); anything else asserts
+    nothing about it.  ``defer``: ``stream_call`` returns once everything is
+    enqueued and ``finish()`` synchronises, checks and returns the outputs -- so
+    that a second call can be put in flight on another stream in between.
+
+    After the call: ``returned_early`` (None without a delay), ``host_ms`` (the
+    wall time of the entry point on the host), ``arena``."""
+
+    def __init__(self, stream, cycles=0, claim=None, fill="ones", defer=False):
+        self.stream, self.cycles, self.claim, self.fill, self.defer = stream, int(cycles), claim, fill, defer
+        self.returned_early = self.host_ms = self.arena = self.finish = None
+
+
+def stream_call(what, device, n, outputs, invoke, real, donor, side=None):
+    """Run ``invoke(workspace address or None, n, stream handle, **inputs)`` under the
+    contract, on the current stream (``side=None``: the device otherwise idle,
+    the workspace zeroed) or as ``side`` says.
+
+    ``real``: name -> device tensor of every array input; ``donor``: the same
+    names -> legal inputs of the same type and shape with other values.  The
+    entry point is handed buffers that hold the donor's values until, in stream
+    order after the delay, the real ones are copied over them, and that take
+    the donor's values again right after the call.  In stream order after the
+    delay as well: the workspace fill and the outputs' sentinels.  So whatever
+    part of a call runs on another stream runs during the delay: it reads the
+    donor's inputs, or its memset is overwritten by the fill, or its output by
+    the sentinel; and a read deferred past the call finds the donor's values
+    again.  Nothing between the delay and the return of ``invoke`` may block
+    the host (HarnessDrained).  On a CPU device ``side`` degrades to the plain
+    call.  Returns ``outputs``."""
+    device = torch.device(device)
+    if device.type != "cuda" or side is None:
+        handle = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else None
+        return contract_call(what, device, n, outputs, lambda ws, n_: invoke(ws, n_, handle, **real),
+                             "zero" if side is None else side.fill)
+    assert set(real) == set(donor), (what, sorted(real), sorted(donor))
+    for k, t in real.items():
+        d = donor[k]
+        assert t.is_cuda and d.is_cuda and t.dtype == d.dtype and t.shape == d.shape and t.data_ptr() != d.data_ptr(), (what, k)
+    # before the delay: every allocation, the guards, the donor's values in the input buffers
+    arena = side.arena = Arena(n, device)
+    bufs = {k: d.clone() for k, d in donor.items()}
+    given = [t for t in outputs.values() if t is not None]
+    for t in given:
+        poison(t)
+    _synchronize(device)                  # (the set-up ran on the current stream; a side stream does not wait for it)
+    s = side.stream if side.stream is not None else torch.cuda.current_stream(device)
+    handle = ctypes.c_void_p(s.cuda_stream)
+    ev = torch.cuda.Event()
+    keep = None
+    try:
+        with torch.cuda.stream(s):
+            if side.cycles:
+                torch.cuda._sleep(side.cycles)
+            ev.record(s)
+            for k, b in bufs.items():
+                b.copy_(real[k])
+            if arena.n:
+                arena.fill(side.fill)
+            for t in given:
+                poison(t)
+            if side.cycles and ev.query():
+                raise HarnessDrained(f"{what}: the set-up drained the stream: the delay of {side.cycles} cycles was over "
+                                     f"before the entry point was called (a defect of the test, not of the library)")
+            t0 = time.perf_counter()
+            keep = invoke(arena.pointer() if arena.n else None, arena.n, handle, **bufs)
+            side.host_ms = (time.perf_counter() - t0) * 1e3
+            side.returned_early = (not ev.query()) if side.cycles else None
+            for k, b in bufs.items():
+                b.copy_(donor[k])
+    except BaseException:
+        s.synchronize()                   # nothing of this call is freed while the stream still uses it
+        raise
+
+    def finish():
+        s.synchronize()
+        nonlocal keep
+        keep = None
+        arena.check_guards(f"{what} [side stream]")
+        assert_written(f"{what} [side stream]", outputs)
+        if side.cycles and side.claim == "async" and not side.returned_early:
+            raise AsynchronyViolation(f"{what}: declared asynchronous, but the call returned after {side.host_ms:.1f} ms "
+                                      f"with the delay queued before it already over: it waited for the stream")
+        return outputs
+
+    side.finish = finish
+    return outputs if side.defer else finish()
+
+
+# ---------------------------------------------------------------------------
 # the entry points of include/irlmx.h that take a workspace
 # ---------------------------------------------------------------------------
 
@@ -178,12 +295,31 @@ def _out(dtype, shape, dev, given=True):
     return torch.empty(shape, dtype=dtype, device=dev) if given else None
 
 
-def _run(name, mdp, op, outputs, call, fill, donor):
-    """``call(lib, ws, n, stream, **inputs)`` is the ctypes call; its result code is checked."""
-    import ctypes
+def _run(name, mdp, op, outputs, call, fill, donor, side=None):
+    """``call(lib, ws, n, stream, **inputs)`` is the ctypes call; its result code is checked.
+
+    ``side`` (a Side): the call goes through ``stream_call`` instead.  Every
+    tensor of ``donor`` then names an input that lands late, and the wrapper's
+    own argument of that name must be a device tensor of the same type and
+    shape (``_in`` passes both through untouched); every other array input
+    must be a device tensor as well -- a host array would be uploaded inside
+    the call and block the host.  ``fill`` and the scalars of ``donor`` are not
+    used (``side.fill`` is)."""
     from irlmx import _lib
     lib = _lib.load()
     n = int(lib.irlmx_workspace_bytes(mdp.struct(), op))
+
+    if side is not None:
+        late = {k: v for k, v in (donor or {}).items() if isinstance(v, torch.Tensor)}
+        params = inspect.signature(call).parameters
+        real = {k: params[k].default for k in late}
+
+        def invoke_on(ws, n, st, **inputs):
+            rc, keep = call(lib, ctypes.c_void_p(ws), n, st if st is not None else _lib.stream_ptr(mdp.device), **inputs)
+            _lib.check(rc, name)
+            return keep
+
+        return stream_call(name, mdp.device, n, outputs, invoke_on, real, late, side)
 
     def invoke(ws, n, **inputs):
         rc, keep = call(lib, ctypes.c_void_p(ws), n, _lib.stream_ptr(mdp.device), **inputs)
@@ -193,7 +329,7 @@ def _run(name, mdp, op, outputs, call, fill, donor):
     return contract_call(name, mdp.device, n, outputs, invoke, fill, donor)
 
 
-def backward_maxent(mdp, reward, terminal, rescale=True, fill="zero", donor=None):
+def backward_maxent(mdp, reward, terminal, rescale=True, fill="zero", donor=None, side=None):
     """irlmx_backward_maxent: {"p_action" [B, S, A], "status" [B]}.  ``donor``: a dict of ``reward``, ``terminal``."""
     from irlmx import _lib
     B, S, A, dev = mdp.batch, mdp.n_states, mdp.n_actions, mdp.device
@@ -204,10 +340,10 @@ def backward_maxent(mdp, reward, terminal, rescale=True, fill="zero", donor=None
         return lib.irlmx_backward_maxent(mdp.struct(), _lib.ptr(r), _lib.ptr(tm), 1 if rescale else 0,
                                          _lib.ptr(out["p_action"]), _lib.ptr(out["status"]), ws, n, st), (r, tm)
 
-    return _run("irlmx_backward_maxent", mdp, _lib.OP_BACKWARD, out, call, fill, donor)
+    return _run("irlmx_backward_maxent", mdp, _lib.OP_BACKWARD, out, call, fill, donor, side)
 
 
-def backward_maxent_extended(mdp, reward, terminal, fill="zero", donor=None):
+def backward_maxent_extended(mdp, reward, terminal, fill="zero", donor=None, side=None):
     """irlmx_backward_maxent_extended: {"p_action", "status"}.  ``donor``: ``reward``, ``terminal``."""
     from irlmx import _lib
     B, S, A, dev = mdp.batch, mdp.n_states, mdp.n_actions, mdp.device
@@ -219,10 +355,10 @@ def backward_maxent_extended(mdp, reward, terminal, fill="zero", donor=None):
                                                   _lib.ptr(out["status"]), ws, n, st), (r, tm)
 
     return _run("irlmx_backward_maxent_extended", mdp, _lib.OP_BACKWARD | _lib.PLAN_EXTENDED_RANGE, out, call, fill,
-                donor)
+                donor, side)
 
 
-def forward_svf(mdp, p_initial, terminal, p_action, eps=1e-5, max_iter=0, fill="zero", donor=None):
+def forward_svf(mdp, p_initial, terminal, p_action, eps=1e-5, max_iter=0, fill="zero", donor=None, side=None):
     """irlmx_forward_svf: {"svf" [B, S], "iterations" [B], "status" [B]}.
     ``donor``: ``p_initial``, ``terminal``, ``p_action``, ``max_iter``."""
     from irlmx import _lib
@@ -237,26 +373,26 @@ def forward_svf(mdp, p_initial, terminal, p_action, eps=1e-5, max_iter=0, fill="
                                      _lib.ptr(out["svf"]), _lib.ptr(out["iterations"]), _lib.ptr(out["status"]), ws, n,
                                      st), (p0, tm, pi)
 
-    return _run("irlmx_forward_svf", mdp, _lib.OP_FORWARD, out, call, fill, donor)
+    return _run("irlmx_forward_svf", mdp, _lib.OP_FORWARD, out, call, fill, donor, side)
 
 
-def soft_backward(mdp, reward, terminal_reward, discount, eps=1e-5, max_iter=0, fill="zero", donor=None):
+def soft_backward(mdp, reward, terminal_reward, discount, eps=1e-5, max_iter=0, fill="zero", donor=None, side=None):
     """irlmx_soft_backward: {"p_action", "value", "iterations", "status"}.  ``donor``: ``reward``, ``max_iter``."""
     from irlmx import _lib
     B, S, A, dev = mdp.batch, mdp.n_states, mdp.n_actions, mdp.device
     out = {"p_action": _out(torch.float64, (B, S, A), dev), "value": _out(torch.float64, (B, S), dev),
            "iterations": _out(torch.int64, (B,), dev), "status": _out(torch.int32, (B,), dev)}
 
-    def call(lib, ws, n, st, reward=reward, max_iter=max_iter):
+    def call(lib, ws, n, st, reward=reward, max_iter=max_iter, terminal_reward=terminal_reward):
         r, phi = _in(reward, torch.float64, (B, S), dev), _in(terminal_reward, torch.float64, (B, S), dev)
         return lib.irlmx_soft_backward(mdp.struct(), _lib.ptr(r), _lib.ptr(phi), float(discount), float(eps),
                                        int(max_iter), _lib.ptr(out["p_action"]), _lib.ptr(out["value"]),
                                        _lib.ptr(out["iterations"]), _lib.ptr(out["status"]), ws, n, st), (r, phi)
 
-    return _run("irlmx_soft_backward", mdp, _lib.OP_SOFT_BACKWARD, out, call, fill, donor)
+    return _run("irlmx_soft_backward", mdp, _lib.OP_SOFT_BACKWARD, out, call, fill, donor, side)
 
 
-def value_iteration(mdp, reward, discount, eps=1e-3, average=False, max_iter=0, fill="zero", donor=None):
+def value_iteration(mdp, reward, discount, eps=1e-3, average=False, max_iter=0, fill="zero", donor=None, side=None):
     """irlmx_value_iteration: {"value", "iterations", "status"}.  ``donor``: ``reward``, ``max_iter``."""
     from irlmx import _lib
     B, S, dev = mdp.batch, mdp.n_states, mdp.device
@@ -269,27 +405,28 @@ def value_iteration(mdp, reward, discount, eps=1e-3, average=False, max_iter=0, 
                                          int(max_iter), _lib.ptr(out["value"]), _lib.ptr(out["iterations"]),
                                          _lib.ptr(out["status"]), ws, n, st), (r,)
 
-    return _run("irlmx_value_iteration", mdp, _lib.OP_VALUE_ITERATION, out, call, fill, donor)
+    return _run("irlmx_value_iteration", mdp, _lib.OP_VALUE_ITERATION, out, call, fill, donor, side)
 
 
-def policy_evaluation(mdp, reward, p_action, discount, terminal=None, eps=1e-3, max_iter=0, fill="zero", donor=None):
+def policy_evaluation(mdp, reward, p_action, discount, terminal=None, eps=1e-3, max_iter=0, fill="zero", donor=None,
+                      side=None):
     """irlmx_policy_evaluation: {"value", "iterations", "status"}.  ``donor``: ``reward``, ``p_action``, ``max_iter``."""
     from irlmx import _lib
     B, S, A, dev = mdp.batch, mdp.n_states, mdp.n_actions, mdp.device
     out = {"value": _out(torch.float64, (B, S), dev), "iterations": _out(torch.int64, (B,), dev),
            "status": _out(torch.int32, (B,), dev)}
 
-    def call(lib, ws, n, st, reward=reward, p_action=p_action, max_iter=max_iter):
+    def call(lib, ws, n, st, reward=reward, p_action=p_action, max_iter=max_iter, terminal=terminal):
         r, pi = _in(reward, torch.float64, (B, S), dev), _in(p_action, torch.float64, (B, S, A), dev)
         tm = _in(terminal, torch.uint8, (B, S), dev)
         return lib.irlmx_policy_evaluation(mdp.struct(), _lib.ptr(r), _lib.ptr(pi), _lib.ptr(tm), float(discount),
                                            float(eps), int(max_iter), _lib.ptr(out["value"]),
                                            _lib.ptr(out["iterations"]), _lib.ptr(out["status"]), ws, n, st), (r, pi, tm)
 
-    return _run("irlmx_policy_evaluation", mdp, _lib.OP_POLICY_EVALUATION, out, call, fill, donor)
+    return _run("irlmx_policy_evaluation", mdp, _lib.OP_POLICY_EVALUATION, out, call, fill, donor, side)
 
 
-def backward_maxent_horizon(mdp, reward, horizon, terminal=None, log_z0=True, fill="zero", donor=None):
+def backward_maxent_horizon(mdp, reward, horizon, terminal=None, log_z0=True, fill="zero", donor=None, side=None):
     """irlmx_backward_maxent_horizon: {"p_action_t" [B, T, S, A], "log_z0" [B, S] or None (``log_z0=False``: NULL),
     "status"}.  ``donor``: ``reward``."""
     from irlmx import _lib
@@ -297,15 +434,15 @@ def backward_maxent_horizon(mdp, reward, horizon, terminal=None, log_z0=True, fi
     out = {"p_action_t": _out(torch.float64, (B, T, S, A), dev), "log_z0": _out(torch.float64, (B, S), dev, log_z0),
            "status": _out(torch.int32, (B,), dev)}
 
-    def call(lib, ws, n, st, reward=reward):
+    def call(lib, ws, n, st, reward=reward, terminal=terminal):
         r, tm = _in(reward, torch.float64, (B, S), dev), _in(terminal, torch.uint8, (B, S), dev)
         return lib.irlmx_backward_maxent_horizon(mdp.struct(), _lib.ptr(r), _lib.ptr(tm), T, _lib.ptr(out["p_action_t"]),
                                                  _lib.ptr(out["log_z0"]), _lib.ptr(out["status"]), ws, n, st), (r, tm)
 
-    return _run("irlmx_backward_maxent_horizon", mdp, _lib.OP_BACKWARD_HORIZON, out, call, fill, donor)
+    return _run("irlmx_backward_maxent_horizon", mdp, _lib.OP_BACKWARD_HORIZON, out, call, fill, donor, side)
 
 
-def forward_svf_horizon(mdp, p_initial, p_action_t, terminal=None, svf_t=True, fill="zero", donor=None):
+def forward_svf_horizon(mdp, p_initial, p_action_t, terminal=None, svf_t=True, fill="zero", donor=None, side=None):
     """irlmx_forward_svf_horizon: {"svf" [B, S], "svf_t" [B, T + 1, S] or None (``svf_t=False``: NULL), "status"}.
     ``donor``: ``p_initial``, ``p_action_t`` (of the same horizon)."""
     from irlmx import _lib
@@ -314,17 +451,18 @@ def forward_svf_horizon(mdp, p_initial, p_action_t, terminal=None, svf_t=True, f
     out = {"svf": _out(torch.float64, (B, S), dev), "svf_t": _out(torch.float64, (B, T + 1, S), dev, svf_t),
            "status": _out(torch.int32, (B,), dev)}
 
-    def call(lib, ws, n, st, p_initial=p_initial, p_action_t=p_action_t):
+    def call(lib, ws, n, st, p_initial=p_initial, p_action_t=p_action_t, terminal=terminal):
         p0, tm = _in(p_initial, torch.float64, (B, S), dev), _in(terminal, torch.uint8, (B, S), dev)
         pi = _in(p_action_t, torch.float64, (B, T, S, A), dev)
         return lib.irlmx_forward_svf_horizon(mdp.struct(), _lib.ptr(p0), _lib.ptr(tm), _lib.ptr(pi), T,
                                              _lib.ptr(out["svf"]), _lib.ptr(out["svf_t"]), _lib.ptr(out["status"]), ws,
                                              n, st), (p0, tm, pi)
 
-    return _run("irlmx_forward_svf_horizon", mdp, _lib.OP_FORWARD_HORIZON, out, call, fill, donor)
+    return _run("irlmx_forward_svf_horizon", mdp, _lib.OP_FORWARD_HORIZON, out, call, fill, donor, side)
 
 
-def soft_backward_horizon(mdp, reward, discount, horizon, terminal=None, value0=True, fill="zero", donor=None):
+def soft_backward_horizon(mdp, reward, discount, horizon, terminal=None, value0=True, fill="zero", donor=None,
+                          side=None):
     """irlmx_soft_backward_horizon: {"p_action_t" [B, T, S, A], "value0" [B, S] or None (``value0=False``: NULL),
     "status"}.  ``donor``: ``reward``."""
     from irlmx import _lib
@@ -332,13 +470,13 @@ def soft_backward_horizon(mdp, reward, discount, horizon, terminal=None, value0=
     out = {"p_action_t": _out(torch.float64, (B, T, S, A), dev), "value0": _out(torch.float64, (B, S), dev, value0),
            "status": _out(torch.int32, (B,), dev)}
 
-    def call(lib, ws, n, st, reward=reward):
+    def call(lib, ws, n, st, reward=reward, terminal=terminal):
         r, tm = _in(reward, torch.float64, (B, S), dev), _in(terminal, torch.uint8, (B, S), dev)
         return lib.irlmx_soft_backward_horizon(mdp.struct(), _lib.ptr(r), _lib.ptr(tm), float(discount), T,
                                                _lib.ptr(out["p_action_t"]), _lib.ptr(out["value0"]),
                                                _lib.ptr(out["status"]), ws, n, st), (r, tm)
 
-    return _run("irlmx_soft_backward_horizon", mdp, _lib.OP_SOFT_BACKWARD_HORIZON, out, call, fill, donor)
+    return _run("irlmx_soft_backward_horizon", mdp, _lib.OP_SOFT_BACKWARD_HORIZON, out, call, fill, donor, side)
 
 
 #: C name -> the function above that calls it: every entry point of include/irlmx.h with a

@@ -3,6 +3,9 @@
 * Coverage: the entry points of include/irlmx.h with a ``void* workspace``
   parameter are exactly the ones abi_call wraps, so a new one cannot stay out
   of tests/test_gpu_call_contract.py's matrix.
+  Likewise the entry points with a ``void* stream`` parameter are exactly the
+  ones tests/test_gpu_stream_order.py has a row for, each with a stated claim
+  about asynchrony.
 * Self-test: on CPU tensors, against stand-in "calls" that write their
   workspace and outputs through host pointers, the checker flags a byte written
   at ``workspace + n``, a byte written just before the workspace, an unwritten
@@ -47,6 +50,30 @@ def test_every_entry_point_with_a_workspace_is_wrapped():
     from irlmx import _lib
     for name, fn in A.WRAPPED.items():
         assert name in _lib.SIGNATURES and callable(fn) and "irlmx_" + fn.__name__ == name, name
+
+
+def declared_with_stream():
+    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    return {name for name, params in re.findall(r"\b(irlmx_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
+            if re.search(r"\bvoid\s*\*\s*stream\b", params)}
+
+
+def test_every_entry_point_with_a_stream_has_a_stream_order_row():
+    import test_gpu_stream_order as SO
+    from irlmx import _lib
+    declared = declared_with_stream()
+    assert len(declared) == 27 and {"irlmx_mdp_properties", "irlmx_dense_gemm", "irlmx_rollout"} <= declared, declared
+    assert declared_with_workspace() <= declared                 # every call with a workspace enqueues work
+    assert declared == set(SO.ENTRY_POINTS), (declared - set(SO.ENTRY_POINTS), set(SO.ENTRY_POINTS) - declared)
+    assert declared <= set(_lib.SIGNATURES)
+    for r in SO.ROWS:                                            # every row states its claim and who judges its bits
+        assert SO.CLAIMS[(r.entry, r.shape)] in (SO.ASYNC, SO.SYNC) and r.judged, r.id
+        assert set(r.keys) <= set(SO.CC.KEYS), r.id
+    ran = {(r.entry, r.shape) for r in SO.ROWS}
+    assert set(SO.CLAIMS) == ran, (set(SO.CLAIMS) - ran, ran - set(SO.CLAIMS))     # no claim without a row that checks it
+    for first, second in SO.PAIRS:
+        assert first in SO.ROW and second in SO.ROW, (first, second)
+    assert len(SO.PAIRS) <= 6
 
 
 # -- the harness against stand-in calls --------------------------------------------------------------
@@ -113,6 +140,29 @@ def test_clean_stand_in_passes(n):
 def test_guard_and_sentinel_faults_are_flagged(fault, message, fill):
     with pytest.raises(A.ContractViolation, match=message):
         StandIn(fault)(fill=fill, donor={"scale": -2.0})
+
+
+def test_side_stream_mode_degrades_on_the_cpu():
+    """``stream_call`` with a Side on a CPU device is the plain call: the same checks, the same bits."""
+    def run(side, fault=None):
+        out = {"value": torch.empty(4, dtype=torch.float64), "status": torch.empty(1, dtype=torch.int32)}
+
+        def invoke(ws, n, stream, x):
+            assert stream is None and ws % A.ALIGN == 0 and n == 256
+            ctypes.memset(ws, 0x3C, n + (fault == "byte at n"))
+            out["value"].copy_(2.0 * x)
+            if fault != "status unwritten":
+                out["status"].fill_(0)
+
+        x = torch.arange(4, dtype=torch.float64)
+        return A.stream_call("stand-in", "cpu", 256, out, invoke, {"x": x}, {"x": x + 1.0}, side)
+
+    side = A.Side(None, cycles=1000, claim="async")
+    A.assert_same_bits("side against plain", run(side), run(None))
+    assert side.returned_early is None and run(side)["value"].tolist() == [0.0, 2.0, 4.0, 6.0]
+    for fault, message in (("byte at n", "guard bytes at or beyond"), ("status unwritten", "entries of status")):
+        with pytest.raises(A.ContractViolation, match=message):
+            run(side, fault)
 
 
 def test_dependence_on_the_fill_is_flagged():
