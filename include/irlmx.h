@@ -61,6 +61,7 @@ extern "C" {
 #define IRLMX_OP_BACKWARD_HORIZON 8  /* 5 and 7 stay unknown ops: tests and tools/sanitize pin both answers */
 #define IRLMX_OP_FORWARD_HORIZON 9
 #define IRLMX_OP_SOFT_BACKWARD_HORIZON 11 /* 10 stays an unknown op too: the same tests pin "unknown op 10" */
+#define IRLMX_OP_VALUE_HORIZON 12 /* irlmx_value_horizon (irlmx_timed.h); 5, 7 and 10 stay unknown ops */
 
 /*
  * Transition model P[from, to, action] of B instances (the reference's dense
@@ -213,6 +214,9 @@ int irlmx_numpy_math(int32_t op, const double* x, double* y, int64_t n, void* st
  *        and DENSE GEMM (2*S - 1 sweeps, no host read)          asynchronous
  *      irlmx_backward_maxent_extended per sweep                 asynchronous
  *      the three *_horizon passes, both shapes                  asynchronous
+ *      irlmx_timed.h: irlmx_value_horizon, both shapes;
+ *        irlmx_rollout_horizon,
+ *        irlmx_demo_log_likelihood_horizon                      asynchronous
  *      irlmx_rollout, irlmx_demo_statistics,
  *        irlmx_demo_log_likelihood, irlmx_numpy_math            asynchronous
  *      the four *_numpy_order calls: STENCIL5 and DENSE

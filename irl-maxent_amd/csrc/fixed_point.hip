@@ -1023,6 +1023,7 @@ static OpQueries op_queries(int op) {
     case IRLMX_OP_BACKWARD_HORIZON:
     case IRLMX_OP_FORWARD_HORIZON:
     case IRLMX_OP_SOFT_BACKWARD_HORIZON:
+    case IRLMX_OP_VALUE_HORIZON:
       return {true, horizon_check_model, horizon_workspace_bytes, horizon_plan};
   }
   return {};

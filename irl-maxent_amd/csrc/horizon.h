@@ -1,5 +1,6 @@
 // Host side of the finite-horizon passes (horizon.hip: IRLMX_OP_BACKWARD_HORIZON,
-// IRLMX_OP_FORWARD_HORIZON; soft_horizon.hip: IRLMX_OP_SOFT_BACKWARD_HORIZON).
+// IRLMX_OP_FORWARD_HORIZON; soft_horizon.hip: IRLMX_OP_SOFT_BACKWARD_HORIZON;
+// timed.hip: IRLMX_OP_VALUE_HORIZON).
 // horizon.hip defines what is not a template; fixed_point.h declares what the
 // model queries ask (horizon_op, horizon_check_model, horizon_workspace_bytes, horizon_plan).
 #pragma once
@@ -17,12 +18,12 @@ __device__ inline size_t hz_pi_row(const Model& m, int T, int b, int t, int s) {
 // per-sweep buffers (the fused kernels keep all of this in LDS)
 struct HzWs {
   int32_t* bad;     // [B] backward: some exp(r) is non-finite
-  double* man[2];   // [B][S] backward mantissas / forward d_t / soft V_t, ping and pong
+  double* man[2];   // [B][S] backward mantissas / forward d_t / soft V_t / value v_t, ping and pong
   int32_t* exp[2];  // [B][S] backward exponents
   size_t total;
 };
 
-// LDS of `op`'s fused kernel: ping and pong of (mantissa, exponent), d_t, or V_t behind the NpTables copy.
+// LDS of `op`'s fused kernel: ping and pong of (mantissa, exponent), of d_t or v_t, or of V_t behind the NpTables copy.
 size_t hz_fused_lds(const Model& m, int op);
 
 // The fused shape of a horizon pass: the thread layout of the ordinary fused

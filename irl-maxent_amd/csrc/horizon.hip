@@ -455,6 +455,7 @@ static void (*hz_fwd_fn(int spt))(HzFwdArgs) {
 
 size_t hz_fused_lds(const Model& m, int op) {
   if (op == IRLMX_OP_BACKWARD_HORIZON) return (size_t)m.S * kExtLdsPerState;
+  // (the forward's d_t and the value pass's v_t need no NpTables copy: 16 * S bytes)
   return (op == IRLMX_OP_SOFT_BACKWARD_HORIZON ? sizeof(NpTables) : 0) + 2 * (size_t)m.S * sizeof(double);
 }
 
@@ -471,7 +472,7 @@ int horizon_fused_min_batch() {
 }
 
 bool hz_fused_shape(const Model& m, int op, FusedShape* out) {
-  // (the op whose fused_pair_ok list the kernels are instantiated from: the soft pass has its own)
+  // (the op whose fused_pair_ok list the kernels are instantiated from: the soft and the value pass have their own)
   const int pairs = op == IRLMX_OP_BACKWARD_HORIZON ? IRLMX_OP_BACKWARD : op == IRLMX_OP_FORWARD_HORIZON ? IRLMX_OP_FORWARD : op;
   if (!fused_shape(m, pairs, out, false)) return false;
   if (out->spt > 1 && m.B < horizon_fused_min_batch()) return false;
@@ -505,7 +506,7 @@ size_t horizon_workspace_bytes(const Model& m, int op) { return hz_carve(m, op, 
 void horizon_plan(const Model& m, int op, int64_t* plan) {
   FusedShape fs;
   if (hz_fused_shape(m, op, &fs)) return plan_fused(plan, fs, hz_fused_lds(m, op));
-  plan_sweep(plan, 1, 0);  // one state per lane; the launch count is the horizon (the soft pass's: + 1)
+  plan_sweep(plan, 1, 0);  // one state per lane; the launch count is the horizon (the soft and the value pass's: + 1)
 }
 
 int hz_check_call(const Model& m, const char* fn, int op, int32_t horizon, size_t bytes, void* ws) {

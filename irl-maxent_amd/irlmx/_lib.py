@@ -27,6 +27,7 @@ OP_BACKWARD, OP_FORWARD, OP_SOFT_BACKWARD, OP_VALUE_ITERATION = 1, 2, 3, 4
 OP_POLICY_EVALUATION = 6   # (5 is not an op: the library has always answered "unknown op 5")
 OP_BACKWARD_HORIZON, OP_FORWARD_HORIZON = 8, 9   # (7 is not an op either)
 OP_SOFT_BACKWARD_HORIZON = 11   # (10 is not an op either)
+OP_VALUE_HORIZON = 12   # irlmx_value_horizon (include/irlmx_timed.h)
 HORIZON_MAX = 1 << 20
 PLAN_NO_RESCALE = 0x100
 PLAN_EXTENDED_RANGE = 0x200
@@ -110,6 +111,16 @@ SIGNATURES = {
     "irlmx_dense_gemm_variant": (ctypes.c_int, [_I32, _I32, _I32, _P]),
 }
 
+# The entry points of include/irlmx_timed.h (time-indexed policies): a table of
+# their own, as the header is a header of its own -- SIGNATURES stays the
+# function list of include/irlmx.h.
+TIMED_SIGNATURES = {
+    "irlmx_rollout_horizon": (ctypes.c_int, [_MDP, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "irlmx_demo_log_likelihood_horizon": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                                                         _P, _P]),
+    "irlmx_value_horizon": (ctypes.c_int, [_MDP, _P, _P, _P, _D, _I32, _P, _P, _P, _P, _SZ, _P]),
+}
+
 _lib = None
 _load_error = None
 
@@ -128,7 +139,7 @@ def load():
                        f"`python -c 'import __graft_entry__ as g; g.build()'`")
         raise ImportError(_load_error) from e
     variant = "IRLMX_LIB" in os.environ   # a diagnostic build may predate newer entry points
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **TIMED_SIGNATURES}.items():
         if variant and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

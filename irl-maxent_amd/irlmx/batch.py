@@ -309,8 +309,8 @@ class BatchedMaxEnt:
     def _stationary_only(self, what):
         if self.horizon is not None:
             raise NotImplementedError(f"{what} takes a stationary policy; with horizon={self.horizon} the policy is "
-                                      "time-indexed [T, S, A] and its rollouts, log-likelihood and policy evaluation "
-                                      "are not implemented")
+                                      "time-indexed [T, S, A]: use sample_horizon, log_likelihood_horizon and "
+                                      "expected_value_difference_horizon")
 
     def log_likelihood(self, states, actions, lengths):
         """Mean per-trajectory log-likelihood of stored demonstrations (``states``
@@ -330,6 +330,55 @@ class BatchedMaxEnt:
             self._work, self.last_backward_sweeps = work, sweeps
         ll, ll_traj, _ = ops.demo_log_likelihood(pi, torch.as_tensor(states, device=pi.device), actions, lengths)
         return ll / ll_traj.shape[1]
+
+    # -- the time-indexed policy of a horizon model ------------------------------
+
+    def _policy_t(self, what, stationary):
+        """pi_t [B, T, S, A] of the current theta on all B instances in original
+        order; theta, the step counter, the active set and the compaction state
+        stay as they are."""
+        if self.horizon is None:
+            raise ValueError(f"{what} takes the time-indexed policy of a horizon model; without a horizon use "
+                             f"{stationary}")
+        work, sweeps = self._work, self.last_backward_sweeps
+        self._work = None          # the full batch, in original order
+        try:
+            return self.backward()
+        finally:
+            self._work, self.last_backward_sweeps = work, sweeps
+
+    def log_likelihood_horizon(self, states, actions, lengths):
+        """:meth:`log_likelihood` for a horizon model: the mean per-trajectory
+        log-likelihood of stored demonstrations (``states`` [B, N, L + 1],
+        ``actions`` [B, N, L], ``lengths`` [B, N], as ``ops.rollout_horizon``
+        returns them) under the current theta's time-indexed policy
+        (``ops.demo_log_likelihood_horizon``'s sum over N), a [B] tensor in
+        original instance order, also after compaction.  Reads theta only."""
+        pi = self._policy_t("log_likelihood_horizon", "log_likelihood")
+        ll, ll_traj, _ = ops.demo_log_likelihood_horizon(pi, torch.as_tensor(states, device=pi.device), actions,
+                                                         lengths)
+        return ll / ll_traj.shape[1]
+
+    def expected_value_difference_horizon(self, true_reward, discount=1.0):
+        """:meth:`expected_value_difference` for a horizon model: ``p0 . (v*_0 -
+        v_pi_0)`` over the model's T steps under ``true_reward`` ([S] or
+        [B, S]), pi the current theta's time-indexed policy, p0 and the
+        terminals this object's own (``ops.expected_value_difference_horizon``):
+        a [B] tensor in original instance order.  Reads theta only."""
+        pi = self._policy_t("expected_value_difference_horizon", "expected_value_difference")
+        B, S = self.batch, self.mdp.n_states
+        r = torch.as_tensor(true_reward, dtype=torch.float64, device=self.theta.device)
+        r = r.expand(B, S) if r.dim() == 1 else r.reshape(B, S)
+        return ops.expected_value_difference_horizon(self.mdp, r.contiguous(), pi, self.p_initial, discount,
+                                                     self.terminal)[0]
+
+    def sample_horizon(self, start, n, seed):
+        """``n`` trajectories of T steps per instance under the current theta's
+        time-indexed policy (``ops.rollout_horizon`` with this object's
+        terminals and ``return_trajectories=True``): its RolloutResult, in
+        original instance order.  Reads theta only."""
+        pi = self._policy_t("sample_horizon", "ops.rollout with backward()'s policy")
+        return ops.rollout_horizon(self.mdp, pi, start, n, seed, terminal=self.terminal, return_trajectories=True)
 
     @classmethod
     def from_trajectories(cls, mdp, states, lengths, terminal, features=None, **kw):
@@ -408,7 +457,9 @@ class BatchedCausalHorizon(BatchedMaxEnt):
     and ``discount`` go through its ``**kw``) are the base class's;
     ``e_features - svf`` is the exact gradient of the demonstrations'
     likelihood.  ``log_likelihood`` and ``expected_value_difference`` raise
-    NotImplementedError, as with any time-indexed policy."""
+    NotImplementedError, as with any time-indexed policy: their twins are
+    ``log_likelihood_horizon``, ``expected_value_difference_horizon`` and
+    ``sample_horizon``."""
 
     def __init__(self, mdp, e_features, p_initial, terminal, horizon, discount=1.0, **kw):
         if kw.pop("causal", False):

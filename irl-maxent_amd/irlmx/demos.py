@@ -99,6 +99,31 @@ def sample_device(mdp, terminal, start, n=200, seed=0, beta=2.0, max_len=None, o
     return out.visits.to(torch.float64) / n, out.starts.to(torch.float64) / n, out.lengths
 
 
+def sample_device_horizon(mdp, p_action_t, start, n=200, seed=0):
+    """Sample ``n`` demonstrations of exactly T steps for every instance of a
+    STENCIL5 or ELL model under the time-indexed policy ``p_action_t``
+    [B, T, S, A], on the device (``ops.rollout_horizon`` without a terminal
+    state: one thread per trajectory) -- the demonstrations of the
+    finite-horizon models, ``BatchedMaxEnt(horizon=T)`` and
+    ``BatchedCausalHorizon``.
+
+    ``start`` and ``seed`` as :func:`sample_device`'s.  Returns what it
+    returns: device tensors ``(e_features [B, S], p_initial [B, S], lengths
+    [B, n])``, here with every length T and ``e_features`` summing to T + 1.
+    "Still alive after T steps" is the normal outcome; a trajectory that met an
+    invalid policy or table row or a start state off the model raises
+    ValueError naming the status."""
+    import torch
+    from . import _lib, ops
+    out = ops.rollout_horizon(mdp, p_action_t, start, n, seed)
+    status = out.status.cpu().numpy()
+    if (status >= _lib.TRAJ_BAD_POLICY).any():
+        worst = int(status.max())
+        raise ValueError(f"sample_device_horizon: {int((status == worst).sum())} of {status.size} demonstrations "
+                         f"stopped with status {worst} ({_lib.TRAJ_NAMES[worst]})")
+    return out.visits.to(torch.float64) / n, out.starts.to(torch.float64) / n, out.lengths
+
+
 def sample(row_val, size, terminal, start, n=200, seed=0, beta=2.0, max_len=None, on_truncate="raise",
            with_truncated=False):
     """Sample ``n`` demonstrations on one STENCIL5 table ``row_val`` [4, 5, S].

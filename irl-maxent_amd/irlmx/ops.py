@@ -33,14 +33,14 @@ SHAPES = {0: "fused", 1: "cluster", 2: "sweep", 3: "dense", 4: "dense-gemm", 5: 
 _OPS = {"backward": _lib.OP_BACKWARD, "forward": _lib.OP_FORWARD, "soft_backward": _lib.OP_SOFT_BACKWARD,
         "value_iteration": _lib.OP_VALUE_ITERATION, "policy_evaluation": _lib.OP_POLICY_EVALUATION,
         "backward_horizon": _lib.OP_BACKWARD_HORIZON, "forward_horizon": _lib.OP_FORWARD_HORIZON,
-        "soft_backward_horizon": _lib.OP_SOFT_BACKWARD_HORIZON}
+        "soft_backward_horizon": _lib.OP_SOFT_BACKWARD_HORIZON, "value_horizon": _lib.OP_VALUE_HORIZON}
 _OPS.update({code: code for code in list(_OPS.values())})   # the _lib.OP_* codes themselves are accepted too
 
 
 def execution_plan(mdp, op, rescale=True, extended_range=False):
     """The kernel plan a call of ``op`` ("backward", "forward", "soft_backward",
     "value_iteration", "policy_evaluation", "backward_horizon",
-    "forward_horizon", "soft_backward_horizon", or its ``_lib.OP_*`` code) on ``mdp``
+    "forward_horizon", "soft_backward_horizon", "value_horizon", or its ``_lib.OP_*`` code) on ``mdp``
     runs on the current device (irlmx_execution_plan):
     shape, tile rows R, ghost rows G, tiles per instance C, instances per launch,
     states per lane, in-tile layout, threads, sequential launches, LDS bytes.
@@ -499,6 +499,29 @@ def rollout_seeds(seed, batch, device):
     return torch.as_tensor(np.array(s, dtype=np.uint64).view(np.int64), device=device)
 
 
+def _rollout_buffers(mdp, start, n, seed, steps, return_trajectories, what):
+    """What :func:`rollout` and :func:`rollout_horizon` share: ``(start [B, n] int32, seeds [B], visits,
+    starts, lengths, status, states, actions)`` -- ``states`` [B, n, steps + 1] and ``actions`` [B, n, steps]
+    prefilled with -1, or None (also for a ``steps`` the call is going to refuse)."""
+    B, S, dev = mdp.batch, mdp.n_states, mdp.device
+    if n < 1:
+        raise ValueError(f"{what}: n={n} < 1")
+    st = torch.as_tensor(start if isinstance(start, torch.Tensor) else np.array(start), device=dev)
+    if st.dim() < 2:
+        st = st.reshape(-1, 1).expand(B, n)
+    st = _i32(st, dev, (B, n))
+    seeds = rollout_seeds(seed, B, dev)
+    visits = torch.empty((B, S), dtype=torch.int64, device=dev)
+    starts = torch.empty((B, S), dtype=torch.int64, device=dev)
+    lengths = torch.empty((B, n), dtype=torch.int32, device=dev)
+    status = torch.empty((B, n), dtype=torch.int32, device=dev)
+    states = actions = None
+    if return_trajectories and 1 <= steps <= _lib.ROLLOUT_MAX_LEN:
+        states = torch.full((B, n, steps + 1), -1, dtype=torch.int32, device=dev)
+        actions = torch.full((B, n, steps), -1, dtype=torch.int32, device=dev)
+    return st, seeds, visits, starts, lengths, status, states, actions
+
+
 def rollout(mdp, p_action, terminal, start, n, max_len, seed, return_trajectories=False):
     """Sample ``n`` trajectories per instance under the policy ``p_action``
     [B, S, A] on the device (irlmx_rollout), one thread per trajectory.
@@ -521,23 +544,10 @@ def rollout(mdp, p_action, terminal, start, n, max_len, seed, return_trajectorie
     lib = _lib.load()
     B, S, A, dev = mdp.batch, mdp.n_states, mdp.n_actions, mdp.device
     n, max_len = int(n), int(max_len)
-    if n < 1:
-        raise ValueError(f"rollout: n={n} < 1")
+    st, seeds, visits, starts, lengths, status, states, actions = _rollout_buffers(mdp, start, n, seed, max_len,
+                                                                                   return_trajectories, "rollout")
     pi = _f64(p_action, mdp, (B, S, A))
     term = terminal.to(device=dev, dtype=torch.uint8).reshape(B, S).contiguous()
-    st = torch.as_tensor(start if isinstance(start, torch.Tensor) else np.array(start), device=dev)
-    if st.dim() < 2:
-        st = st.reshape(-1, 1).expand(B, n)
-    st = _i32(st, dev, (B, n))
-    seeds = rollout_seeds(seed, B, dev)
-    visits = torch.empty((B, S), dtype=torch.int64, device=dev)
-    starts = torch.empty((B, S), dtype=torch.int64, device=dev)
-    lengths = torch.empty((B, n), dtype=torch.int32, device=dev)
-    status = torch.empty((B, n), dtype=torch.int32, device=dev)
-    states = actions = None
-    if return_trajectories and 1 <= max_len <= _lib.ROLLOUT_MAX_LEN:
-        states = torch.full((B, n, max_len + 1), -1, dtype=torch.int32, device=dev)
-        actions = torch.full((B, n, max_len), -1, dtype=torch.int32, device=dev)
     _lib.check(lib.irlmx_rollout(mdp.struct(), _lib.ptr(pi), _lib.ptr(term), _lib.ptr(st), _lib.ptr(seeds), n, max_len,
                                  _lib.ptr(visits), _lib.ptr(starts), _lib.ptr(lengths), _lib.ptr(status),
                                  _lib.ptr(states), _lib.ptr(actions), _lib.stream_ptr(dev)), "rollout")
@@ -600,6 +610,125 @@ def demo_log_likelihood(p_action, states, actions, lengths):
     return ll, ll_traj, status
 
 
+# ---------------------------------------------------------------------------
+# time-indexed policies (include/irlmx_timed.h)
+# ---------------------------------------------------------------------------
+
+def _timed_policy(p_action_t, batch, device, sizes=None):
+    """``p_action_t`` as a contiguous float64 [B, T, S, A] device tensor (``sizes``: the (S, A) it must have)."""
+    pi = torch.as_tensor(p_action_t, dtype=torch.float64, device=device)
+    if pi.dim() != 4 or pi.shape[0] != batch or (sizes is not None and tuple(pi.shape[2:]) != tuple(sizes)):
+        want = "S, A" if sizes is None else f"S = {sizes[0]}, A = {sizes[1]}"
+        raise ValueError(f"p_action_t must be [B = {batch}, T, {want}], got {tuple(pi.shape)}")
+    return pi.contiguous()
+
+
+def rollout_horizon(mdp, p_action_t, start, n, seed, terminal=None, return_trajectories=False):
+    """Sample ``n`` trajectories of T steps per instance under the time-indexed
+    policy ``p_action_t`` [B, T, S, A] on the device (irlmx_rollout_horizon):
+    :func:`rollout` with ``max_len = T`` whose step t draws its action from
+    ``p_action_t[b, t, s]`` -- the same generator, the same ``start`` and
+    ``seed`` forms, the same result tuple.  ``terminal``: ``None`` (no state
+    ends a trajectory) or a uint8 [B, S] mask.  Without a terminal state every
+    trajectory has length T and status ``_lib.TRAJ_TRUNCATED``: "still alive
+    after T steps" is the normal outcome here.  With ``return_trajectories``
+    ``states`` is [B, n, T + 1] and ``actions`` [B, n, T].  A stationary policy
+    repeated T times gives :func:`rollout`'s bits."""
+    lib = _lib.load()
+    B, S, A, dev = mdp.batch, mdp.n_states, mdp.n_actions, mdp.device
+    n = int(n)
+    pi = _timed_policy(p_action_t, B, dev, (S, A))
+    T = int(pi.shape[1])
+    st, seeds, visits, starts, lengths, status, states, actions = _rollout_buffers(mdp, start, n, seed, T,
+                                                                                   return_trajectories, "rollout_horizon")
+    term = _optional_mask(terminal, mdp)
+    _lib.check(lib.irlmx_rollout_horizon(mdp.struct(), _lib.ptr(pi), _lib.ptr(term), _lib.ptr(st), _lib.ptr(seeds), n, T,
+                                         _lib.ptr(visits), _lib.ptr(starts), _lib.ptr(lengths), _lib.ptr(status),
+                                         _lib.ptr(states), _lib.ptr(actions), _lib.stream_ptr(dev)), "rollout_horizon")
+    return RolloutResult(visits, starts, lengths, status, states, actions)
+
+
+def demo_log_likelihood_horizon(p_action_t, states, actions, lengths):
+    """Log-likelihood of stored demonstrations under the time-indexed policy
+    ``p_action_t`` [B, T, S, A] (irlmx_demo_log_likelihood_horizon): ``(ll [B],
+    ll_traj [B, N], status [B, N])`` with ``ll_traj[b, n] = sum_{t < len} log
+    p_action_t[b, t, s_t, a_t]`` (numpy's log, added in step order) and
+    ``ll[b]`` their sum in trajectory order.  ``states`` [B, N, L + 1],
+    ``actions`` [B, N, L], as :func:`rollout_horizon` returns them (L = T) or
+    any other L.  A zero-probability action gives -inf; a trajectory longer
+    than T or with an index out of range gets status ``_lib.TRAJ_BAD_INDEX``
+    and NaN."""
+    lib = _lib.load()
+    dev, B, N, stride, st, ln = _stored(states, lengths)
+    pi = _timed_policy(p_action_t, B, dev)
+    T, S, A = int(pi.shape[1]), int(pi.shape[2]), int(pi.shape[3])
+    if stride > 1:
+        ac = _i32(actions, dev, (B, N, stride - 1))
+    else:
+        ac = torch.zeros(1, dtype=torch.int32, device=dev)   # no trajectory has a step: never read
+    ll = torch.empty(B, dtype=torch.float64, device=dev)
+    ll_traj = torch.empty((B, N), dtype=torch.float64, device=dev)
+    status = torch.empty((B, N), dtype=torch.int32, device=dev)
+    _lib.check(lib.irlmx_demo_log_likelihood_horizon(S, A, B, N, stride, T, _lib.ptr(pi), _lib.ptr(st), _lib.ptr(ac),
+                                                     _lib.ptr(ln), _lib.ptr(ll_traj), _lib.ptr(ll), _lib.ptr(status),
+                                                     _lib.stream_ptr(dev)), "demo_log_likelihood_horizon")
+    return ll, ll_traj, status
+
+
+def value_horizon(mdp, reward, horizon, p_action_t=None, discount=1.0, terminal=None, return_values=False):
+    """Finite-horizon value of ``reward`` over ``T = horizon`` steps
+    (irlmx_value_horizon): from ``v_T = r``, for t = T-1 .. 0, ``v_t = r +
+    discount * sum_a p_action_t[:, t, :, a] * (P_a v_{t+1})`` under the
+    time-indexed policy ``p_action_t`` [B, T, S, A], or with ``p_action_t=None``
+    the optimal value ``v_t = max_a (r + discount * P_a v_{t+1})``.  A visited
+    state contributes its reward, the final one included; with a uint8 [B, S]
+    mask ``terminal`` those states are absorbing, ``v_t = r``.
+
+    Returns ``(value0 [B, S], status [B])`` and with ``return_values`` a third
+    entry ``value_t`` [B, T + 1, S], ``v_0 .. v_T``.  Status is
+    ``_lib.NONFINITE`` exactly where ``value0`` holds a non-finite entry.  At
+    discount 1, ``p0 . value0`` equals ``svf . r`` of
+    :func:`forward_svf_horizon` under the same policy.  STENCIL5 and ELL
+    models; ``execution_plan(mdp, "value_horizon")`` names the shape."""
+    lib = _lib.load()
+    B, S, A = mdp.batch, mdp.n_states, mdp.n_actions
+    r = _f64(reward, mdp, (B, S))
+    T = int(horizon)
+    pi = None
+    if p_action_t is not None:
+        pi = _timed_policy(p_action_t, B, mdp.device, (S, A))
+        if pi.shape[1] != T:
+            raise ValueError(f"p_action_t holds {pi.shape[1]} steps for horizon {T}")
+    term = _optional_mask(terminal, mdp)
+    v0 = torch.empty((B, S), dtype=torch.float64, device=mdp.device)
+    vt = None
+    if return_values:
+        vt = torch.empty((B, (T if 1 <= T <= _lib.HORIZON_MAX else 1) + 1, S), dtype=torch.float64, device=mdp.device)
+    status = torch.empty(B, dtype=torch.int32, device=mdp.device)
+    ws, n = _workspace(mdp, _lib.OP_VALUE_HORIZON)
+    _lib.check(lib.irlmx_value_horizon(mdp.struct(), _lib.ptr(r), _lib.ptr(term), _lib.ptr(pi), float(discount), T,
+                                       _lib.ptr(v0), _lib.ptr(vt), _lib.ptr(status), _lib.ptr(ws), n,
+                                       _lib.stream_ptr(mdp.device)), "value_horizon")
+    return (v0, status, vt) if return_values else (v0, status)
+
+
+def expected_value_difference_horizon(mdp, true_reward, p_action_t, p_initial, discount=1.0, terminal=None):
+    """Expected value difference of a time-indexed policy under the *true*
+    reward over its T steps: ``evd[b] = sum_s p0[b, s] * (v*_0[b, s] -
+    v_pi_0[b, s])``, two :func:`value_horizon` calls and a dot product.
+
+    Returns ``(evd [B], v_opt [B, S], v_pi [B, S])``.  Both values are exact
+    T-step recursions (no convergence test), so ``evd`` is non-negative up to
+    rounding for rows that sum to at most 1."""
+    B, S = mdp.batch, mdp.n_states
+    pi = _timed_policy(p_action_t, B, mdp.device, (S, mdp.n_actions))
+    T = int(pi.shape[1])
+    v_opt, _ = value_horizon(mdp, true_reward, T, None, discount, terminal)
+    v_pi, _ = value_horizon(mdp, true_reward, T, pi, discount, terminal)
+    p0 = _f64(p_initial, mdp, (B, S))
+    return (p0 * (v_opt - v_pi)).sum(dim=1), v_opt, v_pi
+
+
 def dense_gemm(m, z):
     """``z @ m.T`` on the fp64 matrix cores (irlmx_dense_gemm): m [R, S], z [B, S]
     float64 device tensors -> [B, R].  The batched P . [v_1 .. v_B] contraction
@@ -655,4 +784,5 @@ def stochastic_policy(successor, weighted_value):
 __all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "backward_maxent_extended", "backward_maxent_horizon", "forward_svf", "forward_svf_horizon", "soft_backward",
            "soft_backward_horizon",
            "value_iteration", "policy_evaluation", "expected_value_difference", "rollout", "rollout_seeds",
-           "demo_statistics", "demo_log_likelihood", "RolloutResult", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]
+           "demo_statistics", "demo_log_likelihood", "RolloutResult", "rollout_horizon", "demo_log_likelihood_horizon",
+           "value_horizon", "expected_value_difference_horizon", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]

@@ -42,7 +42,12 @@
 //  * the demonstration calls (rollout.hip): every validation path of
 //    irlmx_rollout (NULL arrays, n_traj, max_len below 1 and above its cap,
 //    states without actions, DENSE tables), irlmx_demo_statistics and
-//    irlmx_demo_log_likelihood (sizes, stride, NULL arrays).
+//    irlmx_demo_log_likelihood (sizes, stride, NULL arrays);
+//  * the calls on time-indexed policies (timed.hip, include/irlmx_timed.h): the
+//    plan and workspace of IRLMX_OP_VALUE_HORIZON for every stencil and ELL
+//    model above -- the soft horizon pass's, with 16 * S bytes of LDS when
+//    fused -- and every validation path of irlmx_value_horizon,
+//    irlmx_rollout_horizon and irlmx_demo_log_likelihood_horizon.
 //
 // Exit status 0 and "host_check ok" on success.
 //
@@ -59,6 +64,7 @@
 #include <vector>
 
 #include "../../include/irlmx.h"
+#include "../../include/irlmx_timed.h"
 
 static int g_fail = 0;
 static long long g_checks = 0;
@@ -325,6 +331,41 @@ static void horizon_plan_and_workspace(const irlmx_mdp& m, const char* what) {
   }
 }
 
+// IRLMX_OP_VALUE_HORIZON answers as IRLMX_OP_SOFT_BACKWARD_HORIZON does, except for the fused kernel's LDS.
+static void value_horizon_plan_and_workspace(const irlmx_mdp& m, const char* what) {
+  const int op = IRLMX_OP_VALUE_HORIZON;
+  int64_t p[IRLMX_PLAN_LEN], q[IRLMX_PLAN_LEN];
+  for (auto& v : p) v = -7;
+  for (auto& v : q) v = -7;
+  const int rc = irlmx_execution_plan(&m, op, p);
+  const size_t ws = irlmx_workspace_bytes(&m, op);
+  const int rq = irlmx_execution_plan(&m, IRLMX_OP_SOFT_BACKWARD_HORIZON, q);
+  CHECK(rc == rq && ws == irlmx_workspace_bytes(&m, IRLMX_OP_SOFT_BACKWARD_HORIZON), "%s: value horizon rc %d / %d, workspace %zu",
+        what, rc, rq, ws);
+  if (m.layout == IRLMX_LAYOUT_DENSE) {
+    CHECK(rc == IRLMX_EINVAL && strstr(irlmx_last_error(), "DENSE") && ws == 0, "%s: value horizon plan of a DENSE table rc %d", what, rc);
+    return;
+  }
+  CHECK(rc == 0, "%s: value horizon plan rc %d (%s)", what, rc, irlmx_last_error());
+  if (rc) return;
+  const size_t S = (size_t)m.n_states, B = (size_t)m.batch;
+  for (int i = 0; i < 9; ++i) CHECK(p[i] == q[i], "%s: value horizon plan[%d] %lld, the soft pass's %lld", what, i, (long long)p[i], (long long)q[i]);
+  if (p[0] == IRLMX_SHAPE_FUSED) {
+    CHECK(p[9] == (int64_t)(16 * S) && q[9] == p[9] + 1536 && p[8] == 1 && ws == 0, "%s: value horizon fused LDS %lld workspace %zu", what,
+          (long long)p[9], ws);
+    CHECK(p[5] >= 1 && p[5] <= 4 && p[5] * p[7] >= (int64_t)S && p[7] % 64 == 0 && p[7] <= 1024, "%s: value horizon fused spt %lld threads %lld",
+          what, (long long)p[5], (long long)p[7]);
+  } else {
+    CHECK(p[0] == IRLMX_SHAPE_SWEEP && p[5] == 1 && p[7] == 256 && p[8] == 0 && p[9] == 0, "%s: value horizon sweep plan", what);
+    const size_t floor = B * S * 16;
+    CHECK(ws >= floor && ws <= floor + 2 * 256 && ws % 256 == 0, "%s: value horizon workspace %zu (floor %zu)", what, ws, floor);
+  }
+  CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_EXTENDED_RANGE, p) == IRLMX_EINVAL && strstr(irlmx_last_error(), "IRLMX_OP_BACKWARD only"),
+        "%s: extended flag on the value horizon op", what);
+  CHECK(irlmx_execution_plan(&m, op | IRLMX_PLAN_NO_RESCALE, p) == IRLMX_EINVAL && strstr(irlmx_last_error(), "NO_RESCALE"),
+        "%s: no-rescale flag on the value horizon op", what);
+}
+
 static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
   for (int op = IRLMX_OP_BACKWARD; op <= IRLMX_OP_VALUE_ITERATION; ++op) {
     char what[160];
@@ -342,6 +383,7 @@ static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
       extended_plan_and_workspace(m, what);
       policy_eval_plan_and_workspace(m, what);
       horizon_plan_and_workspace(m, what);
+      value_horizon_plan_and_workspace(m, what);
     }
     const size_t ws = irlmx_workspace_bytes(&m, op);
     const size_t floor = (op == IRLMX_OP_BACKWARD || op == IRLMX_OP_FORWARD)
@@ -391,6 +433,19 @@ static int run_roll(const irlmx_mdp* m, int n_traj, int max_len, void* pi, void*
   return irlmx_rollout(m, (const double*)pi, (const uint8_t*)term, (const int32_t*)start, (const uint64_t*)seed, n_traj,
                        max_len, (int64_t*)visits, (int64_t*)starts, (int32_t*)lengths, (int32_t*)status,
                        (int32_t*)states, (int32_t*)actions, nullptr);
+}
+
+static int run_vhz(const irlmx_mdp* m, void* reward, void* term, void* pi, double discount, int horizon, void* v0, void* vt,
+                   void* status, void* ws, size_t n) {
+  return irlmx_value_horizon(m, (const double*)reward, (const uint8_t*)term, (const double*)pi, discount, horizon, (double*)v0,
+                             (double*)vt, (int32_t*)status, ws, n, nullptr);
+}
+
+static int run_rollhz(const irlmx_mdp* m, int n_traj, int horizon, void* pi, void* term, void* start, void* seed,
+                      void* visits, void* starts, void* lengths, void* status, void* states, void* actions) {
+  return irlmx_rollout_horizon(m, (const double*)pi, (const uint8_t*)term, (const int32_t*)start, (const uint64_t*)seed,
+                               n_traj, horizon, (int64_t*)visits, (int64_t*)starts, (int32_t*)lengths, (int32_t*)status,
+                               (int32_t*)states, (int32_t*)actions, nullptr);
 }
 
 static void expect(int rc, int want, const char* msg_part, const char* what) {
@@ -651,6 +706,80 @@ static void error_paths() {
     expect(irlmx_demo_log_likelihood(25, 4, 1, 8, 17, dbl, i32, i32, i32, dbl, dbl, nullptr, nullptr), IRLMX_EINVAL,
            "traj_status is NULL", "likelihood null status");
   }
+  {  // irlmx_value_horizon, irlmx_rollout_horizon, irlmx_demo_log_likelihood_horizon: every validation path
+    const int op = IRLMX_OP_VALUE_HORIZON;
+    irlmx_mdp big = stencil(128, 40, 4, 2, 0);  // per sweep: v's two buffers (a fused model needs no workspace)
+    const size_t n = irlmx_workspace_bytes(&big, op);
+    CHECK(n >= 2 * 2 * 5120 * sizeof(double) && n % 256 == 0, "value horizon workspace of a per-sweep model: %zu", n);
+    CHECK(irlmx_workspace_bytes(&good, op) == 0, "value horizon workspace of a fused model");
+    expect(run_vhz(nullptr, f, f, f, 0.9, 8, f, f, f, f, n), IRLMX_EINVAL, "mdp is NULL", "value horizon null mdp");
+    expect(run_rollhz(nullptr, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "mdp is NULL", "rollout horizon null mdp");
+    for (const Bad& b : bad) {
+      expect(run_vhz(&b.m, f, f, f, 0.9, 8, f, f, f, f, n), IRLMX_EINVAL, b.msg, b.name);
+      expect(run_rollhz(&b.m, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, b.msg, b.name);
+      CHECK(irlmx_workspace_bytes(&b.m, op) == 0, "%s: value horizon workspace of an invalid model", b.name);
+    }
+    int64_t p[IRLMX_PLAN_LEN];
+    irlmx_mdp d = dense(25, 4, 1);
+    expect(run_vhz(&d, f, f, f, 0.9, 8, f, f, f, f, n), IRLMX_EINVAL, "value_horizon: the finite-horizon passes do not run the DENSE",
+           "value horizon dense");
+    expect(run_rollhz(&d, 8, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL,
+           "rollout_horizon: the finite-horizon passes do not run the DENSE", "rollout horizon dense");
+    expect(irlmx_execution_plan(&d, op, p), IRLMX_EINVAL, "execution_plan: the finite-horizon passes do not run the DENSE",
+           "value horizon plan of a DENSE table");
+    expect(run_vhz(&big, nullptr, f, f, 0.9, 8, f, f, f, f, n), IRLMX_EINVAL, "value_horizon: reward is NULL", "value horizon null reward");
+    expect(run_vhz(&big, f, f, f, 0.9, 8, nullptr, f, f, f, n), IRLMX_EINVAL, "value0 is NULL", "value horizon null value0");
+    expect(run_vhz(&big, f, f, f, 0.9, 8, f, f, nullptr, f, n), IRLMX_EINVAL, "status is NULL", "value horizon null status");
+    for (double g : {-0.1, 1.5, (double)NAN, (double)INFINITY})
+      expect(run_vhz(&big, f, f, f, g, 8, f, f, f, f, n), IRLMX_EINVAL, "outside [0, 1]", "value horizon discount out of range");
+    for (int h : {0, -1, (1 << 20) + 1}) {
+      expect(run_vhz(&big, f, f, f, 0.9, h, f, f, f, f, n), IRLMX_EINVAL, "outside [1, 1048576]", "value horizon out of range");
+      expect(run_rollhz(&good, 8, h, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "outside [1, 1048576]", "rollout horizon out of range");
+      expect(irlmx_demo_log_likelihood_horizon(25, 4, 1, 8, 17, h, (double*)f, (int32_t*)f, (int32_t*)f, (int32_t*)f, (double*)f,
+                                               (double*)f, (int32_t*)f, nullptr),
+             IRLMX_EINVAL, "demo_log_likelihood_horizon: horizon", "likelihood horizon out of range");
+    }
+    // terminal, p_action_t and value_t may be NULL, the discount 0 or 1: the calls get as far as the workspace check
+    expect(run_vhz(&big, f, nullptr, nullptr, 1.0, 1 << 20, f, nullptr, f, f, n - 1), IRLMX_EWORKSPACE, "workspace too small",
+           "value horizon short workspace (terminal, p_action_t and value_t NULL are legal)");
+    expect(run_vhz(&big, f, f, f, 0.0, 8, f, f, f, nullptr, n), IRLMX_EWORKSPACE, "workspace too small", "value horizon null workspace");
+    expect(irlmx_execution_plan(&good, op, p), IRLMX_OK, "", "value horizon plan of a fused model");
+    CHECK(p[0] == IRLMX_SHAPE_FUSED && p[5] == 1 && p[8] == 1 && p[9] == 16 * (int64_t)good.n_states,
+          "value horizon fused plan: shape %lld spt %lld LDS %lld", (long long)p[0], (long long)p[5], (long long)p[9]);
+    expect(irlmx_execution_plan(&big, op, p), IRLMX_OK, "", "value horizon plan of a per-sweep model");
+    CHECK(p[0] == IRLMX_SHAPE_SWEEP && p[5] == 1 && p[7] == 256 && p[8] == 0 && p[9] == 0, "value horizon sweep plan");
+    const char* names[7] = {"p_action_t", "start", "seed", "visits", "starts", "lengths", "traj_status"};
+    for (int i = 0; i < 7; ++i) {
+      void* a[7] = {f, f, f, f, f, f, f};
+      a[i] = nullptr;
+      char msg[64];
+      snprintf(msg, sizeof(msg), "rollout_horizon: %s is NULL", names[i]);
+      expect(run_rollhz(&good, 8, 16, a[0], nullptr, a[1], a[2], a[3], a[4], a[5], a[6], f, f), IRLMX_EINVAL, msg, msg);
+    }
+    expect(run_rollhz(&good, 0, 16, f, f, f, f, f, f, f, f, f, f), IRLMX_EINVAL, "n_traj=0 < 1", "rollout horizon n_traj 0");
+    expect(run_rollhz(&good, 8, 16, f, f, f, f, f, f, f, f, f, nullptr), IRLMX_EINVAL, "both be NULL or both be set",
+           "rollout horizon states without actions");
+    expect(run_rollhz(&good, 8, 16, f, f, f, f, f, f, f, f, nullptr, f), IRLMX_EINVAL, "both be NULL or both be set",
+           "rollout horizon actions without states");
+    int32_t* i32 = (int32_t*)f;
+    double* dbl = (double*)f;
+    expect(irlmx_demo_log_likelihood_horizon(25, 0, 1, 8, 17, 16, dbl, i32, i32, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "demo_log_likelihood_horizon: bad sizes", "timed likelihood A = 0");
+    expect(irlmx_demo_log_likelihood_horizon(25, 4, 1, 0, 17, 16, dbl, i32, i32, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "n_traj=0 < 1", "timed likelihood n_traj 0");
+    expect(irlmx_demo_log_likelihood_horizon(25, 4, 1, 8, 0, 16, dbl, i32, i32, i32, dbl, dbl, i32, nullptr), IRLMX_EINVAL,
+           "stride=0 < 1", "timed likelihood stride 0");
+    const char* lnames[7] = {"p_action_t", "states", "actions", "lengths", "ll_traj", "ll", "traj_status"};
+    for (int i = 0; i < 7; ++i) {
+      void* a[7] = {f, f, f, f, f, f, f};
+      a[i] = nullptr;
+      char msg[80];
+      snprintf(msg, sizeof(msg), "demo_log_likelihood_horizon: %s is NULL", lnames[i]);
+      expect(irlmx_demo_log_likelihood_horizon(25, 4, 1, 8, 17, 16, (double*)a[0], (int32_t*)a[1], (int32_t*)a[2], (int32_t*)a[3],
+                                               (double*)a[4], (double*)a[5], (int32_t*)a[6], nullptr),
+             IRLMX_EINVAL, msg, msg);
+    }
+  }
   expect(irlmx_forward_svf(&good, (double*)f, (uint8_t*)f, (double*)f, 1e-5, 0, (double*)f, nullptr, (int32_t*)f, f,
                            1 << 30, nullptr),
          IRLMX_EINVAL, "iterations is NULL", "forward null iterations");
@@ -750,7 +879,7 @@ static void dump_plans() {
   const int ops[] = {IRLMX_OP_BACKWARD, IRLMX_OP_FORWARD, IRLMX_OP_SOFT_BACKWARD, IRLMX_OP_VALUE_ITERATION,
                      IRLMX_OP_BACKWARD | IRLMX_PLAN_NO_RESCALE, IRLMX_OP_BACKWARD | IRLMX_PLAN_EXTENDED_RANGE,
                      IRLMX_OP_POLICY_EVALUATION, IRLMX_OP_BACKWARD_HORIZON, IRLMX_OP_FORWARD_HORIZON,
-                     IRLMX_OP_SOFT_BACKWARD_HORIZON};
+                     IRLMX_OP_SOFT_BACKWARD_HORIZON, IRLMX_OP_VALUE_HORIZON};
   for (const auto& sw : switches) {
     if (sw[0]) setenv(sw[0], sw[1], 1);
     for_each_model([&](const irlmx_mdp& m, const char* tag) {
