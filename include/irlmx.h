@@ -217,6 +217,8 @@ int irlmx_numpy_math(int32_t op, const double* x, double* y, int64_t n, void* st
  *      irlmx_timed.h: irlmx_value_horizon, both shapes;
  *        irlmx_rollout_horizon,
  *        irlmx_demo_log_likelihood_horizon                      asynchronous
+ *      irlmx_expected_svf.h: irlmx_expected_svf_horizon,
+ *        both shapes                                            asynchronous
  *      irlmx_rollout, irlmx_demo_statistics,
  *        irlmx_demo_log_likelihood, irlmx_numpy_math            asynchronous
  *      the four *_numpy_order calls: STENCIL5 and DENSE

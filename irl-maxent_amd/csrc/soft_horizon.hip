@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "horizon.h"
+#include "horizon_rows.h"
 
 namespace irlmx {
 
@@ -44,36 +45,6 @@ struct ShWs {
   double* v[2];  // [B][S] ping and pong
   size_t total;
 };
-
-// One state of one step: writes the policy row `out`, returns v (step 2).
-// KMAX > 0: the slot class is compiled in, and up to 8 slots the slot loop is
-// unrolled (nbr(k) may then be a register copy); from 16 slots on, and with
-// KMAX = 0 (per-sweep shape: any K), the slot loop is rolled.
-template <int KMAX, class Nbr>
-__device__ __attribute__((always_inline)) inline double sh_row(const Model& m, int b, int s, double r, double discount,
-                                                               const double* vin, Nbr&& nbr, const NpTables* tabs,
-                                                               double* out) {
-  const int K = m.K, A = m.A;
-  double v = 0.0;
-#pragma unroll 1
-  for (int act = 0; act < A; ++act) {
-    double acc = 0.0;
-    if constexpr (KMAX > 0 && KMAX <= 8) {
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K) acc = fma(row_val(m, b, act, k, s), vin[nbr(k)], acc);
-    } else {
-#pragma unroll 1
-      for (int k = 0; k < K; ++k) acc = fma(row_val(m, b, act, k, s), vin[nbr(k)], acc);
-    }
-    const double q = __dadd_rn(r, __dmul_rn(discount, acc));
-    out[act] = q;
-    v = act == 0 ? q : softmax2(v, q, tabs);
-  }
-#pragma unroll 1
-  for (int act = 0; act < A; ++act) out[act] = np_exp(__dsub_rn(out[act], v), tabs);  // maxent.py:341
-  return v;
-}
 
 // ---------------------------------------------------------------------------
 // fused shape: one workgroup per instance for all T steps

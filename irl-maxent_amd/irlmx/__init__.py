@@ -21,5 +21,6 @@ from .ops import expected_value_difference, policy_evaluation  # noqa: F401
 from .ops import demo_log_likelihood, rollout  # noqa: F401
 from .ops import backward_maxent_horizon, forward_svf_horizon, soft_backward_horizon  # noqa: F401
 from .ops import demo_log_likelihood_horizon, expected_value_difference_horizon, rollout_horizon, value_horizon  # noqa: F401
+from .ops import expected_svf_horizon, expected_svf_horizon_plan  # noqa: F401
 
 __version__ = "0.1.0"

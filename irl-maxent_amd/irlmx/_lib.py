@@ -121,6 +121,15 @@ TIMED_SIGNATURES = {
     "irlmx_value_horizon": (ctypes.c_int, [_MDP, _P, _P, _P, _D, _I32, _P, _P, _P, _P, _SZ, _P]),
 }
 
+# The entry points of include/irlmx_expected_svf.h (the finite-horizon expected
+# SVF in one call), a table of their own for the same reason.
+EXPECTED_SVF_SIGNATURES = {
+    "irlmx_expected_svf_horizon": (ctypes.c_int, [_MDP, _I32, _P, _P, _P, _D, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "irlmx_expected_svf_horizon_workspace_bytes": (_SZ, [_MDP, _I32, _I32, _I32]),
+    "irlmx_expected_svf_horizon_plan": (ctypes.c_int, [_MDP, _I32, _I32, _I32, _P]),
+}
+HORIZON_MODEL_MAXENT, HORIZON_MODEL_CAUSAL = 0, 1   # IRLMX_HORIZON_MODEL_*
+
 _lib = None
 _load_error = None
 
@@ -139,7 +148,7 @@ def load():
                        f"`python -c 'import __graft_entry__ as g; g.build()'`")
         raise ImportError(_load_error) from e
     variant = "IRLMX_LIB" in os.environ   # a diagnostic build may predate newer entry points
-    for name, (res, args) in {**SIGNATURES, **TIMED_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **TIMED_SIGNATURES, **EXPECTED_SVF_SIGNATURES}.items():
         if variant and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

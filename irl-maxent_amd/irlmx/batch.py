@@ -62,7 +62,10 @@ instance at T = 128) and ``forward()`` sums the T + 1 marginals
 empty; ``extended_range`` is ignored, the pass always keeps one exponent per
 state.  ``BatchedCausalHorizon`` is the same driver with the finite-horizon
 soft value iteration as its backward pass (``ops.soft_backward_horizon``): the
-MaxCausalEnt model, for stochastic dynamics.
+MaxCausalEnt model, for stochastic dynamics.  ``stream_policy=True`` (or a
+segment length C) on either makes ``step()`` one call of
+``ops.expected_svf_horizon``: the same bits without the policy tensor, memory
+about 2 * sqrt(T) vectors of [n, S] instead of T * A.
 """
 
 import numpy as np
@@ -88,7 +91,7 @@ def terminal_reward(terminal, n_states, batch=1, device=None):
 class BatchedMaxEnt:
     def __init__(self, mdp: DeviceMDP, e_features, p_initial, terminal, features=None, lr0=0.2,
                  eps_esvf=1e-5, theta0=1.0, rescale=True, causal=False, discount=None, eps_lap=1e-5,
-                 optimizer=None, extended_range=False, horizon=None):
+                 optimizer=None, extended_range=False, horizon=None, stream_policy=False):
         """``theta0``: a float (the reference's Constant init, optimizer.py:369-398) or
         an array [F] or [B, F] (e.g. drawn with the reference's Uniform init,
         optimizer.py:334-366).  ``optimizer``: an irlmx.optim optimiser (default
@@ -103,7 +106,12 @@ class BatchedMaxEnt:
         reduction and one host read per step.
         ``horizon``: an int T >= 1 runs the finite-horizon passes (module
         docstring); ``terminal`` may then be empty; ValueError with
-        ``causal=True``."""
+        ``causal=True``.
+        ``stream_policy`` (horizon models only, ValueError without a horizon):
+        ``True`` or an int C makes ``step()`` call ``ops.expected_svf_horizon``
+        (``segment`` = 0 or C) instead of ``backward()`` plus ``forward()``: the
+        same bits without the policy tensor.  ``backward()``, ``forward()`` and
+        the consumers of the time-indexed policy stay as they are."""
         if horizon is not None:
             if causal:
                 raise ValueError("horizon applies to the non-causal model only (the finite-horizon causal model "
@@ -112,6 +120,12 @@ class BatchedMaxEnt:
                 raise ValueError(f"horizon must be an integer in [1, 2^20], got {horizon!r}")
             horizon = int(horizon)
         self.horizon = horizon
+        if stream_policy is not False:
+            if horizon is None:
+                raise ValueError("stream_policy needs a horizon (it streams the time-indexed policy of a horizon model)")
+            if stream_policy is not True and (int(stream_policy) != stream_policy or int(stream_policy) < 0):
+                raise ValueError(f"stream_policy must be False, True or a segment length >= 0, got {stream_policy!r}")
+        self.stream_policy = stream_policy
         if extended_range not in (False, True, "auto"):
             raise ValueError(f"extended_range must be False, True or 'auto', got {extended_range!r}")
         self.extended_range = extended_range
@@ -278,9 +292,30 @@ class BatchedMaxEnt:
         self.k += 1
         return grad
 
+    def _horizon_model(self):
+        """``(model, discount)`` of ``ops.expected_svf_horizon`` for this driver's backward pass."""
+        return "maxent", 1.0
+
+    def expected_svf(self):
+        """``(svf [n, S], sweeps [n], status [n])`` of the working set in one call,
+        without the time-indexed policy (``ops.expected_svf_horizon``): what
+        ``forward(backward())`` returns, bit for bit.  Horizon models only."""
+        if self.horizon is None:
+            raise ValueError("expected_svf runs the one-call pass of a horizon model; without a horizon use "
+                             "forward(backward())")
+        model, discount = self._horizon_model()
+        auto = self.stream_policy is False or self.stream_policy is True      # (1 == True: identity, not equality)
+        segment = 0 if auto else int(self.stream_policy)
+        r = self.reward(self._theta_w(), self._w("features"))
+        return ops.expected_svf_horizon(self._w("mdp"), r, self._w("p_initial"), self.horizon, model=model,
+                                        discount=discount, terminal=self._w("terminal"), segment=segment)
+
     def step(self):
-        pi = self.backward()
-        svf, iters, _ = self.forward(pi)
+        if self.stream_policy is not False:
+            svf, iters, _ = self.expected_svf()
+        else:
+            pi = self.backward()
+            svf, iters, _ = self.forward(pi)
         self.last_forward_sweeps = self._scatter(iters)
         self.update(svf)
         return svf
@@ -476,3 +511,6 @@ class BatchedCausalHorizon(BatchedMaxEnt):
         """The time-indexed policy [n, T, S, A] of the working set."""
         r = self.reward(self._theta_w(), self._w("features"))
         return ops.soft_backward_horizon(self._w("mdp"), r, self.discount, self.horizon, self._w("terminal"))
+
+    def _horizon_model(self):
+        return "causal", self.discount

@@ -428,6 +428,71 @@ def forward_svf_horizon(mdp, p_initial, p_action_t, terminal=None, return_margin
     return (svf, sweeps, status, marg) if return_marginals else (svf, sweeps, status)
 
 
+_HORIZON_MODELS = {"maxent": _lib.HORIZON_MODEL_MAXENT, "causal": _lib.HORIZON_MODEL_CAUSAL,
+                   _lib.HORIZON_MODEL_MAXENT: _lib.HORIZON_MODEL_MAXENT,
+                   _lib.HORIZON_MODEL_CAUSAL: _lib.HORIZON_MODEL_CAUSAL}
+EXPECTED_SVF_PLAN_FIELDS = ("shape", "segment", "slices", "launches", "lds_bytes", "workspace_bytes")
+
+
+def _horizon_model(model):
+    if model not in _HORIZON_MODELS:
+        raise ValueError(f'model must be "maxent" or "causal", got {model!r}')
+    return _HORIZON_MODELS[model]
+
+
+def expected_svf_horizon_plan(mdp, horizon, model="maxent", segment=0):
+    """The plan of :func:`expected_svf_horizon` with these arguments
+    (irlmx_expected_svf_horizon_plan): shape ("fused" or "sweep", one launch
+    per step), the segment length C as resolved, the [B, S] slices held,
+    launches (0: one per step), LDS bytes and workspace bytes."""
+    import ctypes
+    lib = _lib.load()
+    buf = (ctypes.c_int64 * len(EXPECTED_SVF_PLAN_FIELDS))()
+    _lib.check(lib.irlmx_expected_svf_horizon_plan(mdp.struct(), _horizon_model(model), int(horizon), int(segment), buf),
+               "expected_svf_horizon_plan")
+    plan = dict(zip(EXPECTED_SVF_PLAN_FIELDS, [int(v) for v in buf]))
+    plan["shape"] = SHAPES[plan["shape"]]
+    return plan
+
+
+def expected_svf_horizon(mdp, reward, p_initial, horizon, model="maxent", discount=1.0, terminal=None, segment=0,
+                         return_objective=False):
+    """Expected state visitation of ``T = horizon`` steps straight from the
+    reward (irlmx_expected_svf_horizon): what :func:`backward_maxent_horizon`
+    (``model="maxent"``) or :func:`soft_backward_horizon` (``model="causal"``,
+    with ``discount`` in [0, 1]) followed by :func:`forward_svf_horizon`
+    returns, bit for bit, without the policy tensor ``pi_t`` [B, T, S, A].
+
+    The backward's state is kept every ``segment`` = C steps and each segment
+    is recomputed when the forward pass reaches it, so the workspace holds about
+    ``T / C + C`` vectors of [B, S] instead of ``T * A``: ``segment=0`` takes
+    C = ceil(sqrt(T)), a value above T keeps every step (no recomputation).
+
+    Returns ``(svf [B, S], sweeps [B] int64 -- T for every instance --, status
+    [B] int32)`` and with ``return_objective`` a fourth entry [B, S]: ``log_z0``
+    for "maxent", ``V_0`` for "causal".  Status is ``_lib.NONFINITE`` exactly
+    where either call of the two-call path reports it.  STENCIL5 and ELL
+    models; :func:`expected_svf_horizon_plan` names the shape."""
+    lib = _lib.load()
+    B, S = mdp.batch, mdp.n_states
+    code = _horizon_model(model)
+    T, C = int(horizon), int(segment)
+    r = _f64(reward, mdp, (B, S))
+    p0 = _f64(p_initial, mdp, (B, S))
+    term = _optional_mask(terminal, mdp)
+    svf = torch.empty((B, S), dtype=torch.float64, device=mdp.device)
+    obj = torch.empty((B, S), dtype=torch.float64, device=mdp.device) if return_objective else None
+    status = torch.empty(B, dtype=torch.int32, device=mdp.device)
+    # (from torch's allocator on the current stream, as _workspace: 0 bytes for arguments the call refuses)
+    n = int(lib.irlmx_expected_svf_horizon_workspace_bytes(mdp.struct(), code, T, C))
+    ws = torch.empty(max(n, 256), dtype=torch.uint8, device=mdp.device)
+    _lib.check(lib.irlmx_expected_svf_horizon(mdp.struct(), code, _lib.ptr(r), _lib.ptr(term), _lib.ptr(p0),
+                                              float(discount), T, C, _lib.ptr(svf), _lib.ptr(obj), _lib.ptr(status),
+                                              _lib.ptr(ws), n, _lib.stream_ptr(mdp.device)), "expected_svf_horizon")
+    sweeps = torch.full((B,), T, dtype=torch.int64, device=mdp.device)
+    return (svf, sweeps, status, obj) if return_objective else (svf, sweeps, status)
+
+
 def _row_targets(mdp):
     """Target state of every stored slot, int64 [tables, K, S] on the device."""
     if mdp.layout == _lib.LAYOUT_ELL:
@@ -782,7 +847,7 @@ def stochastic_policy(successor, weighted_value):
 
 
 __all__ = ["DeviceMDP", "execution_plan", "numpy_order_default", "counters", "terminal_mask", "backward_maxent", "backward_maxent_extended", "backward_maxent_horizon", "forward_svf", "forward_svf_horizon", "soft_backward",
-           "soft_backward_horizon",
+           "soft_backward_horizon", "expected_svf_horizon", "expected_svf_horizon_plan",
            "value_iteration", "policy_evaluation", "expected_value_difference", "rollout", "rollout_seeds",
            "demo_statistics", "demo_log_likelihood", "RolloutResult", "rollout_horizon", "demo_log_likelihood_horizon",
            "value_horizon", "expected_value_difference_horizon", "dense_gemm", "dense_gemm_variant", "optimal_policy", "stochastic_policy"]

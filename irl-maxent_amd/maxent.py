@@ -223,6 +223,14 @@ def irl(p_transition, features, terminal, trajectories, optim, init, eps=1e-4, e
 
 # -- finite horizon (no reference counterpart) ---------------------------------
 
+def _streamed_svf(mdp, reward, p0, horizon, term, stream_policy, model, discount=1.0):
+    """``stream_policy`` (True, or an int segment length) of the horizon drop-ins:
+    ``ops.expected_svf_horizon``, the two passes in one call without the policy tensor."""
+    segment = 0 if stream_policy is True else int(stream_policy)
+    return ops.expected_svf_horizon(mdp, reward, p0, horizon, model=model, discount=discount, terminal=term,
+                                    segment=segment)[0]
+
+
 def _horizon_mask(mdp, terminal):
     """The terminal mask, or None for an empty ``terminal`` (no terminal state)."""
     return ops.terminal_mask(terminal, mdp.n_states, device=mdp.device) if np.size(terminal) else None
@@ -237,25 +245,32 @@ def local_action_probabilities_horizon(p_transition, terminal, reward, horizon):
     return _host(ops.backward_maxent_horizon(mdp, reward, horizon, _horizon_mask(mdp, terminal)))
 
 
-def compute_expected_svf_horizon(p_transition, p_initial, terminal, reward, horizon):
+def compute_expected_svf_horizon(p_transition, p_initial, terminal, reward, horizon, stream_policy=False):
     """Expected state visitation over the T + 1 states of a ``horizon``-step
     trajectory: the finite-horizon backward then forward pass
-    (``ops.forward_svf_horizon``).  Sums to T + 1 without terminals."""
+    (``ops.forward_svf_horizon``).  Sums to T + 1 without terminals.
+    ``stream_policy`` (True, or an int segment length): the same bits from
+    ``ops.expected_svf_horizon``, without the [T, S, A] policy in memory."""
     mdp = _model(p_transition)
     term = _horizon_mask(mdp, terminal)
+    if stream_policy is not False:
+        return _host(_streamed_svf(mdp, reward, p_initial, horizon, term, stream_policy, "maxent"))
     pi = ops.backward_maxent_horizon(mdp, reward, horizon, term)
     svf, _, _ = ops.forward_svf_horizon(mdp, p_initial, pi, term)
     return _host(svf)
 
 
-def irl_horizon(p_transition, features, terminal, trajectories, optim, init, horizon, eps=1e-4):
+def irl_horizon(p_transition, features, terminal, trajectories, optim, init, horizon, eps=1e-4, stream_policy=False):
     """MaxEnt IRL with the finite-horizon model: ``irl``'s gradient ascent, the
-    expected visitation from ``compute_expected_svf_horizon``.  For
-    demonstrations of ``horizon`` steps each; ``terminal`` may be ``[]``."""
+    expected visitation from ``compute_expected_svf_horizon`` (``stream_policy``
+    as there).  For demonstrations of ``horizon`` steps each; ``terminal`` may
+    be ``[]``."""
     mdp = _model(p_transition)
     term_h = _horizon_mask(mdp, terminal)
 
     def svf_fn(m, reward, term, p0):
+        if stream_policy is not False:
+            return _host(_streamed_svf(m, reward, p0, horizon, term_h, stream_policy, "maxent"))
         pi = ops.backward_maxent_horizon(m, reward, horizon, term_h)
         svf, _, _ = ops.forward_svf_horizon(m, p0, pi, term_h)
         return _host(svf)
@@ -272,26 +287,35 @@ def local_causal_action_probabilities_horizon(p_transition, terminal, reward, di
     return _host(ops.soft_backward_horizon(mdp, reward, discount, horizon, _horizon_mask(mdp, terminal)))
 
 
-def compute_expected_causal_svf_horizon(p_transition, p_initial, terminal, reward, discount, horizon):
+def compute_expected_causal_svf_horizon(p_transition, p_initial, terminal, reward, discount, horizon,
+                                        stream_policy=False):
     """Expected state visitation over the T + 1 states of a ``horizon``-step
     trajectory under the finite-horizon MaxCausalEnt policy: the soft Bellman
-    recursion, then ``ops.forward_svf_horizon``."""
+    recursion, then ``ops.forward_svf_horizon``.  ``stream_policy`` (True, or
+    an int segment length): the same bits from ``ops.expected_svf_horizon``,
+    without the [T, S, A] policy in memory."""
     mdp = _model(p_transition)
     term = _horizon_mask(mdp, terminal)
+    if stream_policy is not False:
+        return _host(_streamed_svf(mdp, reward, p_initial, horizon, term, stream_policy, "causal", discount))
     pi = ops.soft_backward_horizon(mdp, reward, discount, horizon, term)
     svf, _, _ = ops.forward_svf_horizon(mdp, p_initial, pi, term)
     return _host(svf)
 
 
-def irl_causal_horizon(p_transition, features, terminal, trajectories, optim, init, discount, horizon, eps=1e-4):
+def irl_causal_horizon(p_transition, features, terminal, trajectories, optim, init, discount, horizon, eps=1e-4,
+                       stream_policy=False):
     """MaxCausalEnt IRL with the finite-horizon model: ``irl_causal``'s gradient
     ascent, the expected visitation from ``compute_expected_causal_svf_horizon``
-    (the exact gradient of the demonstrations' likelihood).  For demonstrations
-    of ``horizon`` steps each; ``terminal`` may be ``[]``."""
+    (the exact gradient of the demonstrations' likelihood; ``stream_policy`` as
+    there).  For demonstrations of ``horizon`` steps each; ``terminal`` may be
+    ``[]``."""
     mdp = _model(p_transition)
     term_h = _horizon_mask(mdp, terminal)
 
     def svf_fn(m, reward, term, p0):
+        if stream_policy is not False:
+            return _host(_streamed_svf(m, reward, p0, horizon, term_h, stream_policy, "causal", discount))
         pi = ops.soft_backward_horizon(m, reward, discount, horizon, term_h)
         svf, _, _ = ops.forward_svf_horizon(m, p0, pi, term_h)
         return _host(svf)

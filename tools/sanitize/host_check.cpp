@@ -47,7 +47,13 @@
 //    plan and workspace of IRLMX_OP_VALUE_HORIZON for every stencil and ELL
 //    model above -- the soft horizon pass's, with 16 * S bytes of LDS when
 //    fused -- and every validation path of irlmx_value_horizon,
-//    irlmx_rollout_horizon and irlmx_demo_log_likelihood_horizon.
+//    irlmx_rollout_horizon and irlmx_demo_log_likelihood_horizon;
+//  * the one-call expected SVF (expected_svf_horizon.hip,
+//    include/irlmx_expected_svf.h): irlmx_expected_svf_horizon_workspace_bytes
+//    and irlmx_expected_svf_horizon_plan for every model above, both models,
+//    horizons 1 .. 2^20 and the segment lengths 0, 1, 3, T and T + 5 -- the
+//    resolved segment, the slices, the shape and the header's memory bound --
+//    and every validation path of irlmx_expected_svf_horizon.
 //
 // Exit status 0 and "host_check ok" on success.
 //
@@ -64,6 +70,7 @@
 #include <vector>
 
 #include "../../include/irlmx.h"
+#include "../../include/irlmx_expected_svf.h"
 #include "../../include/irlmx_timed.h"
 
 static int g_fail = 0;
@@ -366,6 +373,44 @@ static void value_horizon_plan_and_workspace(const irlmx_mdp& m, const char* wha
         "%s: no-rescale flag on the value horizon op", what);
 }
 
+// The one-call expected SVF's size and plan for one model (include/irlmx_expected_svf.h)
+static long long g_esh_shapes[3];
+static void expected_svf_plan_and_workspace(const irlmx_mdp& m, const char* what) {
+  const size_t B = m.batch, S = m.n_states, A = m.n_actions;
+  const bool dense = m.layout == IRLMX_LAYOUT_DENSE;
+  const int64_t kc = m.layout == IRLMX_LAYOUT_STENCIL5 ? 5 : m.k_col;
+  for (int model : {IRLMX_HORIZON_MODEL_MAXENT, IRLMX_HORIZON_MODEL_CAUSAL})
+    for (int T : {1, 2, 40, 4096, 1 << 20})
+      for (int seg : {0, 1, 3, T, T + 5}) {
+        int64_t p[6];
+        for (auto& v : p) v = -7;
+        const int rc = irlmx_expected_svf_horizon_plan(&m, model, T, seg, p);
+        const size_t ws = irlmx_expected_svf_horizon_workspace_bytes(&m, model, T, seg);
+        if (dense) {
+          CHECK(rc == IRLMX_EINVAL && strstr(irlmx_last_error(), "expected_svf_horizon: the finite-horizon passes do not run the DENSE") && ws == 0,
+                "%s: expected svf plan of a DENSE table rc %d ws %zu", what, rc, ws);
+          continue;
+        }
+        CHECK(rc == 0, "%s: expected svf plan rc %d (%s)", what, rc, irlmx_last_error());
+        if (rc) continue;
+        int64_t C = seg > T ? T : seg;
+        if (seg == 0)
+          for (C = 1; C * C < T; ++C) {}
+        const int64_t nseg = (T + C - 1) / C;
+        CHECK(p[1] == C && p[2] == nseg + C - 1 + (nseg > 1 ? 2 : 0), "%s: expected svf T %d segment %d: C %lld slices %lld", what, T,
+              seg, (long long)p[1], (long long)p[2]);
+        const size_t lds = (model == IRLMX_HORIZON_MODEL_CAUSAL ? 1536 : 0) + 8 * S * (A + 2);
+        const bool fused = S <= 1024 && kc <= 32 && lds <= 160 * 1024;
+        CHECK(p[0] == (fused ? IRLMX_SHAPE_FUSED : IRLMX_SHAPE_SWEEP) && p[3] == (fused ? 1 : 0) && p[4] == (fused ? (int64_t)lds : 0),
+              "%s: expected svf shape %lld launches %lld LDS %lld", what, (long long)p[0], (long long)p[3], (long long)p[4]);
+        CHECK(p[5] == (int64_t)ws && ws % 256 == 0 && ws >= (size_t)p[2] * B * S * (model == IRLMX_HORIZON_MODEL_MAXENT ? 12 : 8),
+              "%s: expected svf workspace %zu, plan %lld", what, ws, (long long)p[5]);
+        CHECK(ws <= (size_t)(nseg + C + (int64_t)A + 6) * B * S * 12 + 4096, "%s: expected svf workspace %zu above the bound (T %d C %lld)",
+              what, ws, T, (long long)C);
+        if (T == 40 && seg == 0) ++g_esh_shapes[p[0]];
+      }
+}
+
 static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
   for (int op = IRLMX_OP_BACKWARD; op <= IRLMX_OP_VALUE_ITERATION; ++op) {
     char what[160];
@@ -384,6 +429,7 @@ static void plan_and_workspace(const irlmx_mdp& m, const char* tag) {
       policy_eval_plan_and_workspace(m, what);
       horizon_plan_and_workspace(m, what);
       value_horizon_plan_and_workspace(m, what);
+      expected_svf_plan_and_workspace(m, what);
     }
     const size_t ws = irlmx_workspace_bytes(&m, op);
     const size_t floor = (op == IRLMX_OP_BACKWARD || op == IRLMX_OP_FORWARD)
@@ -439,6 +485,12 @@ static int run_vhz(const irlmx_mdp* m, void* reward, void* term, void* pi, doubl
                    void* status, void* ws, size_t n) {
   return irlmx_value_horizon(m, (const double*)reward, (const uint8_t*)term, (const double*)pi, discount, horizon, (double*)v0,
                              (double*)vt, (int32_t*)status, ws, n, nullptr);
+}
+
+static int run_esh(const irlmx_mdp* m, int model, void* reward, void* term, void* p0, double discount, int horizon,
+                   int segment, void* svf, void* obj, void* status, void* ws, size_t n) {
+  return irlmx_expected_svf_horizon(m, model, (const double*)reward, (const uint8_t*)term, (const double*)p0, discount, horizon,
+                                    segment, (double*)svf, (double*)obj, (int32_t*)status, ws, n, nullptr);
 }
 
 static int run_rollhz(const irlmx_mdp* m, int n_traj, int horizon, void* pi, void* term, void* start, void* seed,
@@ -599,6 +651,45 @@ static void error_paths() {
     expect(irlmx_execution_plan(&wide, IRLMX_OP_FORWARD_HORIZON, p), IRLMX_OK, "", "horizon forward plan K_c = 3");
     CHECK(p[0] == IRLMX_SHAPE_FUSED, "horizon forward plan K_c = 3: shape %lld", (long long)p[0]);
     expect(irlmx_execution_plan(&good, IRLMX_OP_FORWARD_HORIZON + 1, p), IRLMX_EINVAL, "unknown op 10", "op 10");
+  }
+  {  // irlmx_expected_svf_horizon: every validation path, in the order the entry checks them
+    const int ME = IRLMX_HORIZON_MODEL_MAXENT, CA = IRLMX_HORIZON_MODEL_CAUSAL;
+    const size_t n = irlmx_expected_svf_horizon_workspace_bytes(&good, ME, 8, 0);
+    CHECK(n > 0 && n % 256 == 0 && n > irlmx_expected_svf_horizon_workspace_bytes(&good, CA, 8, 0), "expected svf workspaces: %zu", n);
+    expect(run_esh(nullptr, ME, f, f, f, 1.0, 8, 0, f, f, f, f, n), IRLMX_EINVAL, "mdp is NULL", "expected svf null mdp");
+    int64_t p[6];
+    for (const Bad& b : bad) {
+      expect(run_esh(&b.m, ME, f, f, f, 1.0, 8, 0, f, f, f, f, n), IRLMX_EINVAL, b.msg, b.name);
+      expect(irlmx_expected_svf_horizon_plan(&b.m, ME, 8, 0, p), IRLMX_EINVAL, b.msg, b.name);
+      CHECK(irlmx_expected_svf_horizon_workspace_bytes(&b.m, ME, 8, 0) == 0, "%s: expected svf workspace of an invalid model", b.name);
+    }
+    irlmx_mdp d = dense(25, 4, 1);
+    expect(run_esh(&d, ME, f, f, f, 1.0, 8, 0, f, f, f, f, n), IRLMX_EINVAL,
+           "expected_svf_horizon: the finite-horizon passes do not run the DENSE", "expected svf dense");
+    irlmx_mdp nocol = ell(25, 4, 3, 3, 1);
+    nocol.col_idx = nullptr;
+    expect(run_esh(&nocol, ME, f, f, f, 1.0, 8, 0, f, f, f, f, n), IRLMX_EINVAL, "ELL column form missing", "expected svf without columns");
+    for (int model : {-1, 2})
+      expect(run_esh(&good, model, f, f, f, 1.0, 8, 0, f, f, f, f, n), IRLMX_EINVAL, "is neither IRLMX_HORIZON_MODEL_MAXENT nor",
+             "expected svf model");
+    for (int h : {0, -1, (1 << 20) + 1})
+      expect(run_esh(&good, CA, f, f, f, 1.0, h, 0, f, f, f, f, n), IRLMX_EINVAL, "expected_svf_horizon: horizon", "expected svf horizon");
+    expect(run_esh(&good, ME, f, f, f, 1.0, 8, -1, f, f, f, f, n), IRLMX_EINVAL, "segment -1 is negative", "expected svf segment");
+    expect(run_esh(&good, ME, nullptr, f, f, 1.0, 8, 0, f, f, f, f, n), IRLMX_EINVAL, "expected_svf_horizon: reward is NULL", "expected svf null reward");
+    expect(run_esh(&good, ME, f, f, nullptr, 1.0, 8, 0, f, f, f, f, n), IRLMX_EINVAL, "p_initial is NULL", "expected svf null p_initial");
+    expect(run_esh(&good, ME, f, f, f, 1.0, 8, 0, nullptr, f, f, f, n), IRLMX_EINVAL, "svf is NULL", "expected svf null svf");
+    expect(run_esh(&good, ME, f, f, f, 1.0, 8, 0, f, f, nullptr, f, n), IRLMX_EINVAL, "status is NULL", "expected svf null status");
+    for (double g : {-0.1, 1.5, (double)NAN})
+      expect(run_esh(&good, CA, f, f, f, g, 8, 0, f, f, f, f, n), IRLMX_EINVAL, "outside [0, 1]", "expected svf causal discount");
+    for (double g : {0.9, 0.0, (double)NAN})
+      expect(run_esh(&good, ME, f, f, f, g, 8, 0, f, f, f, f, n), IRLMX_EINVAL, "outside {1} (MAXENT)", "expected svf maxent discount");
+    // terminal and objective0 may be NULL: the calls get as far as the workspace check
+    expect(run_esh(&good, ME, f, nullptr, f, 1.0, 1 << 20, 0, f, nullptr, f, f, n), IRLMX_EWORKSPACE,
+           "expected_svf_horizon: workspace too small", "expected svf short workspace (terminal and objective0 NULL are legal)");
+    expect(run_esh(&good, CA, f, f, f, 0.0, 8, 0, f, f, f, f, 0), IRLMX_EWORKSPACE, "workspace too small", "expected svf no workspace");
+    expect(run_esh(&good, ME, f, f, f, 1.0, 8, 0, f, f, f, f, n - 1), IRLMX_EWORKSPACE, "workspace too small", "expected svf short workspace");
+    expect(run_esh(&good, ME, f, f, f, 1.0, 8, 0, f, f, f, nullptr, n), IRLMX_EWORKSPACE, "workspace too small", "expected svf null workspace");
+    expect(irlmx_expected_svf_horizon_plan(&good, ME, 8, 0, nullptr), IRLMX_EINVAL, "plan is NULL", "expected svf null plan");
   }
   {  // irlmx_soft_backward_horizon: every validation path, in the order the entry checks them
     const int op = IRLMX_OP_SOFT_BACKWARD_HORIZON;
@@ -933,6 +1024,8 @@ int main(int argc, char** argv) {
         g_pe_shapes[0], g_pe_shapes[2]);
   CHECK(g_hz_shapes[0] > 200 && g_hz_shapes[2] > 200, "horizon shapes planned: fused %lld sweep %lld", g_hz_shapes[0],
         g_hz_shapes[2]);
+  CHECK(g_esh_shapes[0] > 200 && g_esh_shapes[2] > 200, "expected svf shapes planned: fused %lld per step %lld", g_esh_shapes[0],
+        g_esh_shapes[2]);
   if (g_fail) {
     fprintf(stderr, "host_check: %d of %lld checks failed\n", g_fail, g_checks);
     return 1;
