@@ -17,10 +17,11 @@
 //            into one [S][A] buffer, one forward step under them, D += d_{t+1}
 //
 // which holds ceil(T/C) + C slices of [B][S] instead of T * A.  Every per-state
-// statement is the one horizon.hip and soft_horizon.hip run (horizon_rows.h);
-// a value-only step runs the same operations on the value and leaves out the
-// division (MAXENT) or the exp of the row (CAUSAL), on which no value depends.
-// So svf, objective0 and status carry the bits of the two-call path for every C.
+// function is the one horizon.hip and soft_horizon.hip run (horizon_rows.h:
+// hz_row_loop, sh_row); a value-only step instantiates the same function with
+// ROW = false, which compiles out the division (MAXENT) or the exp of the row
+// (CAUSAL), on which no value depends.  So svf, objective0 and status carry the
+// bits of the two-call path for every C.
 //
 // Two shapes, the same statements in both: per step -- one launch over all
 // instances per value step, policy step and forward step, everything in the
@@ -77,45 +78,8 @@ __host__ __device__ inline int esh_slice_seg(int nseg, int j, int lo, int hi, in
   return t == hi ? j : nseg + (t - lo - 1);
 }
 
-// The value of hz_row_loop: its statements without the division.
-__device__ inline double esh_zsum(const Model& m, int b, int s, double er, const double* zm, const int* ze, int* Eout) {
-  const int K = m.K, A = m.A;
-  int E = kExtZero;
-  for (int k = 0; k < K; ++k) {
-    bool any = false;
-    for (int act = 0; act < A; ++act) any |= row_val(m, b, act, k, s) != 0.0;
-    if (any) E = max(E, ze[row_nbr(m, b, s, k)]);
-  }
-  double zsum = 0.0;
-  for (int act = 0; act < A; ++act) {
-    double acc = 0.0;
-    for (int k = 0; k < K; ++k) {
-      const int n = row_nbr(m, b, s, k);
-      acc = fma(row_val(m, b, act, k, s), ext_aligned(zm[n], ze[n], E), acc);
-    }
-    zsum = __dadd_rn(zsum, __dmul_rn(er, acc));
-  }
-  *Eout = E;
-  return zsum;
-}
-
-// The value of sh_row<0>: its statements without the row.
-__device__ inline double esh_soft_v(const Model& m, int b, int s, double r, double discount, const double* vin,
-                                    const NpTables* tabs) {
-  const int K = m.K, A = m.A;
-  double v = 0.0;
-#pragma unroll 1
-  for (int act = 0; act < A; ++act) {
-    double acc = 0.0;
-#pragma unroll 1
-    for (int k = 0; k < K; ++k) acc = fma(row_val(m, b, act, k, s), vin[row_nbr(m, b, s, k)], acc);
-    const double q = __dadd_rn(r, __dmul_rn(discount, acc));
-    v = act == 0 ? q : softmax2(v, q, tabs);
-  }
-  return v;
-}
-
-// One state of a value-only step: X_t(s) into slice `so` from X_{t+1} in slice `si`.
+// One state of a value-only step: X_t(s) into slice `so` from X_{t+1} in slice
+// `si`, by the ROW = false forms of the functions esh_policy_state calls.
 template <int MODEL>
 __device__ __attribute__((always_inline)) inline void esh_value_state(const EshArgs& a, const EshWs& ws, int b, int s,
                                                                       int si, int so, const NpTables* tabs) {
@@ -132,14 +96,17 @@ __device__ __attribute__((always_inline)) inline void esh_value_state(const EshA
       ext_split(er, 0, &zm, &ze);  // absorbing: Z_t = exp(r), held
     } else {
       int E;
-      const double zsum = esh_zsum(m, b, s, er, ws.xm + in, ws.xe + in, &E);
+      const double zsum = hz_row_loop<false>(m, b, s, er, ws.xm + in, ws.xe + in, nullptr, &E);
       ext_split(zsum, E, &zm, &ze);
     }
     ws.xm[out] = zm;
     ws.xe[out] = ze;
   } else {
     const double r = a.reward[i];
-    ws.xm[out] = term ? r : esh_soft_v(m, b, s, r, a.discount, ws.xm + in, tabs);
+    ws.xm[out] = term ? r
+                      : sh_row<0, false>(m, b, s, r, a.discount, ws.xm + in,
+                                         [&](int k) __attribute__((always_inline)) { return row_nbr(m, b, s, k); },
+                                         tabs, nullptr);
   }
 }
 

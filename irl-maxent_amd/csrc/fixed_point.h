@@ -343,7 +343,7 @@ constexpr bool fused_pair_ok(int op, int spt, int kmax) {
       return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 4) || (kmax == 16 && spt == 1) ||
              (kmax == 32 && spt == 1);
     case IRLMX_OP_SOFT_BACKWARD_HORIZON:  // (soft_horizon.hip: rolled action loop, table re-read every step)
-    case IRLMX_OP_VALUE_HORIZON:          // (timed.hip: the same loops without exp / log)
+    case IRLMX_OP_VALUE_HORIZON:          // (the same skeleton and loops without exp / log)
       return (kmax == 5 && spt <= 4) || (kmax == 8 && spt <= 2) || (kmax == 16 && spt <= 2) ||
              (kmax == 32 && spt == 1);
   }
@@ -404,8 +404,8 @@ void extended_plan(const Model& m, int64_t* plan);
 // IRLMX_EINVAL and the message, prefixed by `fn`).
 int policy_eval_check_model(const Model& m, const char* fn);
 
-// The finite-horizon passes (horizon.hip, soft_horizon.hip, timed.hip's
-// IRLMX_OP_VALUE_HORIZON; the rest of their host side is horizon.h): whether this model is one they run (else
+// The finite-horizon passes (horizon.hip, soft_horizon.hip; the rest of their
+// host side is horizon.h): whether this model is one they run (else
 // IRLMX_EINVAL and the message, prefixed by `fn`), their workspace and plan.
 inline bool horizon_op(int op) {
   return op == IRLMX_OP_BACKWARD_HORIZON || op == IRLMX_OP_FORWARD_HORIZON || op == IRLMX_OP_SOFT_BACKWARD_HORIZON ||

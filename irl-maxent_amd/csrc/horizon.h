@@ -1,7 +1,8 @@
 // Host side of the finite-horizon passes (horizon.hip: IRLMX_OP_BACKWARD_HORIZON,
-// IRLMX_OP_FORWARD_HORIZON; soft_horizon.hip: IRLMX_OP_SOFT_BACKWARD_HORIZON;
-// timed.hip: IRLMX_OP_VALUE_HORIZON; expected_svf_horizon.hip routes by
-// hz_fused_shape and has no op code).  Their per-state device functions are
+// IRLMX_OP_FORWARD_HORIZON; soft_horizon.hip: IRLMX_OP_SOFT_BACKWARD_HORIZON and
+// IRLMX_OP_VALUE_HORIZON; expected_svf_horizon.hip routes by hz_fused_shape and
+// has no op code; rollout.hip takes hz_pi_row and the horizon's range for its
+// calls on time-indexed policies).  Their per-state device functions are
 // horizon_rows.h's.
 // horizon.hip defines what is not a template; fixed_point.h declares what the
 // model queries ask (horizon_op, horizon_check_model, horizon_workspace_bytes, horizon_plan).

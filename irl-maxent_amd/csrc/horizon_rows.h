@@ -2,8 +2,10 @@
 // soft_horizon.hip and expected_svf_horizon.hip so that all three compile the
 // same text: the MaxEnt backward row (hz_row with its slot class compiled in,
 // hz_row_loop with run-time loops) and hz_log_z, the MaxCausalEnt backward row
-// (sh_row), and the forward step's folded weight and state (hz_fwd_weight,
-// hz_fwd_state).
+// (sh_row) and the value pass's row (tp_row, its slot loop slot_dot), and
+// the forward step's folded weight and state (hz_fwd_weight, hz_fwd_state).
+// hz_row_loop and sh_row have a value-only form (ROW = false): the same
+// function with the statements that only the policy row needs compiled out.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -91,7 +93,10 @@ __device__ __attribute__((always_inline)) inline double hz_row(int K, int A, dou
   return zsum;
 }
 
-// The same statements with run-time loops (per-sweep shape: any K).
+// The same statements with run-time loops (per-sweep shape: any K).  ROW =
+// false is the value alone (expected_svf_horizon.hip's value-only steps): no
+// za[], no division and nothing written to `out`, on which zsum does not depend.
+template <bool ROW = true>
 __device__ inline double hz_row_loop(const Model& m, int b, int s, double er, const double* zm, const int* ze,
                                      double* out, int* Eout) {
   const int K = m.K, A = m.A;
@@ -101,7 +106,7 @@ __device__ inline double hz_row_loop(const Model& m, int b, int s, double er, co
     for (int act = 0; act < A; ++act) any |= row_val(m, b, act, k, s) != 0.0;
     if (any) E = max(E, ze[row_nbr(m, b, s, k)]);
   }
-  double za[kMaxActions];
+  double za[ROW ? kMaxActions : 1];
   double zsum = 0.0;
   for (int act = 0; act < A; ++act) {
     double acc = 0.0;
@@ -109,10 +114,12 @@ __device__ inline double hz_row_loop(const Model& m, int b, int s, double er, co
       const int n = row_nbr(m, b, s, k);
       acc = fma(row_val(m, b, act, k, s), ext_aligned(zm[n], ze[n], E), acc);
     }
-    za[act] = __dmul_rn(er, acc);
-    zsum = __dadd_rn(zsum, za[act]);
+    const double z = __dmul_rn(er, acc);
+    if constexpr (ROW) za[act] = z;
+    zsum = __dadd_rn(zsum, z);
   }
-  for (int act = 0; act < A; ++act) out[act] = za[act] / zsum;
+  if constexpr (ROW)
+    for (int act = 0; act < A; ++act) out[act] = za[act] / zsum;
   *Eout = E;
   return zsum;
 }
@@ -152,11 +159,35 @@ __device__ inline double hz_fwd_state(const Model& m, int b, int t, const double
   return acc;
 }
 
-// One state of one step: writes the policy row `out`, returns v (step 2).
-// KMAX > 0: the slot class is compiled in, and up to 8 slots the slot loop is
-// unrolled (nbr(k) may then be a register copy); from 16 slots on, and with
-// KMAX = 0 (per-sweep shape: any K), the slot loop is rolled.
+// acc = fma(P[s, target_k(s), act], vin[target_k(s)], acc) from 0 over the
+// slots in slot order.  KMAX > 0: the slot class is compiled in, and up to 8
+// slots the loop is unrolled (nbr(k) may then be a register copy); from 16
+// slots on, and with KMAX = 0 (per-sweep shape: any K), it is rolled.
 template <int KMAX, class Nbr>
+__device__ __attribute__((always_inline)) inline double slot_dot(const Model& m, int b, int act, int s,
+                                                                 const double* vin, Nbr&& nbr) {
+  const int K = m.K;
+  double acc = 0.0;
+  if constexpr (KMAX > 0 && KMAX <= 8) {
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) acc = fma(row_val(m, b, act, k, s), vin[nbr(k)], acc);
+  } else {
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) acc = fma(row_val(m, b, act, k, s), vin[nbr(k)], acc);
+  }
+  return acc;
+}
+
+// One state of one soft step (soft_horizon.hip's steps 1 - 3): writes the
+// policy row `out`, returns v.  ROW = false is the value alone
+// (expected_svf_horizon.hip's value-only steps): q_a is not parked in `out` and
+// the closing exp of the row, on which v does not depend, is absent.
+// The slot loop is slot_dot's, written out: called, the inlined loop's exit
+// block is laid out behind the loop, and next to the inlined exp / log that
+// costs expected_svf_horizon.hip's fused CAUSAL kernel three more spilled SGPRs
+// and the soft step up to 1 % of its time (profiles/horizon_fold_resources.txt).
+template <int KMAX, bool ROW = true, class Nbr>
 __device__ __attribute__((always_inline)) inline double sh_row(const Model& m, int b, int s, double r, double discount,
                                                                const double* vin, Nbr&& nbr, const NpTables* tabs,
                                                                double* out) {
@@ -174,12 +205,35 @@ __device__ __attribute__((always_inline)) inline double sh_row(const Model& m, i
       for (int k = 0; k < K; ++k) acc = fma(row_val(m, b, act, k, s), vin[nbr(k)], acc);
     }
     const double q = __dadd_rn(r, __dmul_rn(discount, acc));
-    out[act] = q;
+    if constexpr (ROW) out[act] = q;
     v = act == 0 ? q : softmax2(v, q, tabs);
   }
+  if constexpr (ROW) {
 #pragma unroll 1
-  for (int act = 0; act < A; ++act) out[act] = np_exp(__dsub_rn(out[act], v), tabs);  // maxent.py:341
+    for (int act = 0; act < A; ++act) out[act] = np_exp(__dsub_rn(out[act], v), tabs);  // maxent.py:341
+  }
   return v;
+}
+
+// One state of one step of the value pass (soft_horizon.hip's value steps
+// 1 - 3; the terminal rule is the caller's).  `pis`: the policy row pi_t(s, :)
+// or null (the optimal value).
+template <int KMAX, class Nbr>
+__device__ __attribute__((always_inline)) inline double tp_row(const Model& m, int b, int s, double r, double discount,
+                                                               const double* vin, Nbr&& nbr, const double* pis) {
+  const int A = m.A;
+  double v = 0.0;  // the running maximum, or the policy's expectation e
+#pragma unroll 1
+  for (int act = 0; act < A; ++act) {
+    const double acc = slot_dot<KMAX>(m, b, act, s, vin, nbr);
+    if (pis) {
+      v = fma(pis[act], acc, v);
+    } else {
+      const double q = __dadd_rn(r, __dmul_rn(discount, acc));
+      v = act == 0 ? q : ((v != v || q <= v) ? v : q);  // irlmx_value_iteration's maximum
+    }
+  }
+  return pis ? __dadd_rn(r, __dmul_rn(discount, v)) : v;
 }
 
 }  // namespace irlmx

@@ -647,6 +647,23 @@ def demo_statistics(n_states, states, lengths):
     return visits, starts, status
 
 
+def _demo_ll(fn, name, dev, B, N, stride, horizon, pi, st, actions, ln):
+    """What the two log-likelihood calls share once the policy is checked: the
+    actions, the outputs and one checked call of ``fn`` (``horizon``: the sizes
+    between ``stride`` and the policy, ``(T,)`` or none)."""
+    S, A = int(pi.shape[-2]), int(pi.shape[-1])
+    if stride > 1:
+        ac = _i32(actions, dev, (B, N, stride - 1))
+    else:
+        ac = torch.zeros(1, dtype=torch.int32, device=dev)   # no trajectory has a step: never read
+    ll = torch.empty(B, dtype=torch.float64, device=dev)
+    ll_traj = torch.empty((B, N), dtype=torch.float64, device=dev)
+    status = torch.empty((B, N), dtype=torch.int32, device=dev)
+    _lib.check(fn(S, A, B, N, stride, *horizon, _lib.ptr(pi), _lib.ptr(st), _lib.ptr(ac), _lib.ptr(ln),
+                  _lib.ptr(ll_traj), _lib.ptr(ll), _lib.ptr(status), _lib.stream_ptr(dev)), name)
+    return ll, ll_traj, status
+
+
 def demo_log_likelihood(p_action, states, actions, lengths):
     """Log-likelihood of stored demonstrations under the policy ``p_action``
     [B, S, A] (irlmx_demo_log_likelihood): ``(ll [B], ll_traj [B, N], status
@@ -660,19 +677,8 @@ def demo_log_likelihood(p_action, states, actions, lengths):
     pi = torch.as_tensor(p_action, dtype=torch.float64, device=dev)
     if pi.dim() != 3 or pi.shape[0] != B:
         raise ValueError(f"p_action must be [B = {B}, S, A], got {tuple(pi.shape)}")
-    pi = pi.contiguous()
-    S, A = int(pi.shape[1]), int(pi.shape[2])
-    if stride > 1:
-        ac = _i32(actions, dev, (B, N, stride - 1))
-    else:
-        ac = torch.zeros(1, dtype=torch.int32, device=dev)   # no trajectory has a step: never read
-    ll = torch.empty(B, dtype=torch.float64, device=dev)
-    ll_traj = torch.empty((B, N), dtype=torch.float64, device=dev)
-    status = torch.empty((B, N), dtype=torch.int32, device=dev)
-    _lib.check(lib.irlmx_demo_log_likelihood(S, A, B, N, stride, _lib.ptr(pi), _lib.ptr(st), _lib.ptr(ac), _lib.ptr(ln),
-                                             _lib.ptr(ll_traj), _lib.ptr(ll), _lib.ptr(status), _lib.stream_ptr(dev)),
-               "demo_log_likelihood")
-    return ll, ll_traj, status
+    return _demo_ll(lib.irlmx_demo_log_likelihood, "demo_log_likelihood", dev, B, N, stride, (), pi.contiguous(), st,
+                    actions, ln)
 
 
 # ---------------------------------------------------------------------------
@@ -726,18 +732,8 @@ def demo_log_likelihood_horizon(p_action_t, states, actions, lengths):
     lib = _lib.load()
     dev, B, N, stride, st, ln = _stored(states, lengths)
     pi = _timed_policy(p_action_t, B, dev)
-    T, S, A = int(pi.shape[1]), int(pi.shape[2]), int(pi.shape[3])
-    if stride > 1:
-        ac = _i32(actions, dev, (B, N, stride - 1))
-    else:
-        ac = torch.zeros(1, dtype=torch.int32, device=dev)   # no trajectory has a step: never read
-    ll = torch.empty(B, dtype=torch.float64, device=dev)
-    ll_traj = torch.empty((B, N), dtype=torch.float64, device=dev)
-    status = torch.empty((B, N), dtype=torch.int32, device=dev)
-    _lib.check(lib.irlmx_demo_log_likelihood_horizon(S, A, B, N, stride, T, _lib.ptr(pi), _lib.ptr(st), _lib.ptr(ac),
-                                                     _lib.ptr(ln), _lib.ptr(ll_traj), _lib.ptr(ll), _lib.ptr(status),
-                                                     _lib.stream_ptr(dev)), "demo_log_likelihood_horizon")
-    return ll, ll_traj, status
+    return _demo_ll(lib.irlmx_demo_log_likelihood_horizon, "demo_log_likelihood_horizon", dev, B, N, stride,
+                    (int(pi.shape[1]),), pi, st, actions, ln)
 
 
 def value_horizon(mdp, reward, horizon, p_action_t=None, discount=1.0, terminal=None, return_values=False):

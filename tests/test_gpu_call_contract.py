@@ -75,8 +75,8 @@ irlmx_backward_maxent_horizon / irlmx_forward_svf_horizon (hz_carve(), horizon.h
   man[0], exp[0]   hz_bwd_init_kernel / hz_fwd_init_kernel (the forward has no exp)
   man[1], exp[1]   the first hz_*_step_kernel, before the second reads them
   irlmx_soft_backward_horizon (the same hz_carve(): man[0..1] alone, as the forward; its kernels' v[0..1]):
-  v[0]    soft_hz_init_kernel writes all of it
-  v[1]    the first soft_hz_step_kernel, before the second reads it
+  v[0]    value_hz_init_kernel<SoftPass> writes all of it
+  v[1]    the first value_hz_step_kernel<SoftPass>, before the second reads it
 
 irlmx_policy_evaluation (carve(), fixed_point.hip; policy_eval.hip):
   wgt     pe_weights_kernel writes all of it; read by pe_fused_kernel / pe_sweep_kernel

@@ -1,6 +1,6 @@
 """The calls on time-indexed policies on the device (needs an MI355X):
 ops.rollout_horizon, ops.demo_log_likelihood_horizon, ops.value_horizon and
-ops.expected_value_difference_horizon (csrc/timed.hip, include/irlmx_timed.h)
+ops.expected_value_difference_horizon (include/irlmx_timed.h; csrc/rollout.hip, csrc/soft_horizon.hip)
 against tests/timed_twin.py on tests/horizon_twin.py's cases, and the three
 driver methods built on them.
 

@@ -1,5 +1,5 @@
 """CPU twin and longdouble restatement of the calls on time-indexed policies
-(include/irlmx_timed.h, csrc/timed.hip); not a test module.  Models and cases
+(include/irlmx_timed.h; csrc/rollout.hip, csrc/soft_horizon.hip); not a test module.  Models and cases
 come from tests/horizon_twin.py, the generator, ``pick`` and the log from
 tests/rollout_twin.py.
 

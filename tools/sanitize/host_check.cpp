@@ -43,7 +43,8 @@
 //    irlmx_rollout (NULL arrays, n_traj, max_len below 1 and above its cap,
 //    states without actions, DENSE tables), irlmx_demo_statistics and
 //    irlmx_demo_log_likelihood (sizes, stride, NULL arrays);
-//  * the calls on time-indexed policies (timed.hip, include/irlmx_timed.h): the
+//  * the calls on time-indexed policies (include/irlmx_timed.h; the value pass
+//    in soft_horizon.hip, the two trajectory calls in rollout.hip): the
 //    plan and workspace of IRLMX_OP_VALUE_HORIZON for every stencil and ELL
 //    model above -- the soft horizon pass's, with 16 * S bytes of LDS when
 //    fused -- and every validation path of irlmx_value_horizon,
